@@ -2,6 +2,24 @@
 """bench.py — Mray/s and ms/frame of the gfx950 radiance path on the BASELINE.json metric config.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3|C2|C4|C5|R-C4|R-main]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it uploads the scene, counts the frame's
+rays (one untimed launch), warms up, times the K steps, writes the last timed frame with
+--dump-outputs, and prints the result line (value, ms_per_step, the roofline of the timed kernel from
+the committed counters).  --full adds the side measurements and checks, each a run of its own after
+the timed region: host_path (gi_render with host buffers, gi_multi_render), cpu_baseline (the CPU port,
+which also checks the timed frame's rows bit for bit), reference_cpu (the compiled reference) and, for
+N > 1, frame_check (the gathered frame against a single-GPU render); --no-cpu-baseline and
+--no-host-path leave one of them out of a --full run.
+
+--dump-outputs DIR: what the timed path left in its last step, as the caller receives it, written by
+rank 0 after the timed region: DIR/rgb.npy (float64, the fp64 radiance; N = 1 and --full runs) and
+DIR/rgb8.npy (float32 holding the RGB888 values), each (pixels, 3) in row-major pixel order.  An array
+over its byte budget (rgb 50 MB, rgb8 12 MB: 62 MB in all) holds a fixed sample of the frame's pixels
+instead -- numpy's default_rng(DUMP_SEED).choice(w * h, n, replace=False), sorted -- so two builds
+run with the same arguments write the same pixels.  The scenes are procedural and seeded: the inputs
+are identical from run to run.
 
 N > 1 is launched by the driver as `torch.distributed.run --nproc-per-node N bench.py --gpus N ...`:
 one rank per GPU (RCCL over xGMI).  The frame's 8x8 pixel tiles are dealt round-robin to the
@@ -29,7 +47,7 @@ algorithmic record bytes (Mode X: wide-node records x 256 B -- 128 B for the qua
 large HBM-resident scenes -- + primitive records x 80 B + 27 B/pixel output; Mode R: 64 B nodes +
 144 B triangles) per launch / that time stay beside it as hbm_alg_frac, and traffic = the HBM bytes
 the counters saw (hbm_counter_frac): the records live in LDS / L2, so the two differ 10-100x.
-cpu_baseline: this repo's CPU port of the same integrator (oracle, test infrastructure), OpenMP over
+cpu_baseline (--full): this repo's CPU port of the same integrator (oracle, test infrastructure), OpenMP over
 the job's CPU share and on 1 thread, on full-width rows spread over the same frame (Mode X: those
 rows also checked against the timed GPU frame, bit for bit); reference_cpu: the compiled reference itself (depth 1, the
 only depth it has) on a strided sample of the same frame, when oracle/_ref is present.
@@ -362,19 +380,55 @@ def host_path(gi, sc, dev, cam, light, w, h, mode, spp, depth, seed, reps=3):
                     "= gi_multi_render, the drop-in's GI_DEVICES route, on this one device); not `value`"}
 
 
-def main():
+DUMP_SEED = 2019                                     # of the pixel sample of a frame over its budget
+DUMP_BUDGET = {"rgb": 50_000_000, "rgb8": 12_000_000}   # bytes per dumped array (62 MB in all)
+
+
+def dump_pixels(n_pixels: int, name: str, itemsize: int):
+    """The pixels DIR/<name>.npy holds: None = the whole frame; else the sorted, seeded sample of as
+    many pixels as the array's byte budget holds (3 channels of `itemsize` bytes each)."""
+    import numpy as np
+    keep = DUMP_BUDGET[name] // (3 * itemsize)
+    if n_pixels <= keep:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_pixels, keep, replace=False))
+
+
+def dump_outputs(torch, out_dir, w, h, rgb, rgb8):
+    """--dump-outputs: the frame the last timed step left in the device buffers (rgb fp64 or None,
+    rgb8 uint8; flat w * h * 3) -> out_dir/rgb.npy (float64), out_dir/rgb8.npy (float32)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t, dt in (("rgb", rgb, np.float64), ("rgb8", rgb8, np.float32)):
+        if t is None:
+            continue
+        px = t.view(w * h, 3)
+        idx = dump_pixels(w * h, name, np.dtype(dt).itemsize)
+        if idx is not None:
+            px = px[torch.from_numpy(idx).to(px.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), px.cpu().numpy().astype(dt, copy=False))
+
+
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="C3", choices=sorted(WORKLOADS))
     ap.add_argument("--seed", type=int, default=2019)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side measurements and checks: host_path, "
+                         "cpu_baseline, reference_cpu, and frame_check for N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's frame to DIR/rgb.npy (float64) and DIR/rgb8.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline and reference_cpu")
     ap.add_argument("--no-host-path", action="store_true",
-                    help="skip the host-buffer gi_render timings (profiling runs: only the timed frames launch)")
+                    help="--full without the host-buffer gi_render timings")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL over xGMI) for real runs; gloo rehearses N ranks sharing one GPU")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -474,12 +528,18 @@ def main():
         elapsed, kern_ms, render_ms = t.tolist()
 
     frame_check = None
-    if world > 1:   # after timing: the last frame's fp64 radiance too, for the check below
+    if world > 1 and args.full:   # after timing: the last frame's fp64 radiance too, for the check below
         fg.gather(radiance=True)
         if rank == 0:
             gi.unshard_device(w, h, world, fg.packed_all.data_ptr(), fg.packed_all8.data_ptr(), frame.data_ptr(),
                               frame8.data_ptr(), sptr)
-    if world > 1 and rank == 0:   # the assembled frame against a whole frame rendered here alone
+    if args.dump_outputs and rank == 0:   # what the last timed step left (N > 1: its RGB888 frame on rank 0;
+        torch.cuda.synchronize()          # the fp64 radiance is gathered by --full only)
+        if world == 1:
+            dump_outputs(torch, args.dump_outputs, w, h, buf, buf8)
+        else:
+            dump_outputs(torch, args.dump_outputs, w, h, frame if args.full else None, frame8)
+    if world > 1 and rank == 0 and args.full:   # the assembled frame against a whole frame rendered here alone
         ref = torch.empty(w * h * 3, dtype=torch.float64, device="cuda")
         ref8 = torch.empty(w * h * 3, dtype=torch.uint8, device="cuda")
         dev.render_device(cam, sc.light, w, h, ref.data_ptr(), ref8.data_ptr(), sptr,
@@ -619,12 +679,12 @@ def main():
                                "cycle_share": {k: round(st[i] / max(1, st[gi.STAT_X_CYC_ALL]), 4) for k, i in
                                                (("traverse", gi.STAT_X_CYC_TRAV), ("consume", gi.STAT_X_CYC_HIT),
                                                 ("next_ray", gi.STAT_X_CYC_NEXT))}}
-        if world == 1 and not args.no_host_path:
+        if args.full and world == 1 and not args.no_host_path:
             out["host_path"] = host_path(gi, sc, dev, cam, sc.light, w, h, mode, spp, depth, args.seed)
             # SURVEY §8(d) ms/frame: the end-to-end gi_render time with the framebuffer's D2H copy
             # (RGB888, the reference Image's content) included
             out["ms_per_frame_with_d2h"] = out["host_path"]["ms_per_frame"]["rgb8"]
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             scn = sc.to_scn()
             gf = None
             if mode == 1:   # the last timed frame (deterministic: every timed frame is this one)
