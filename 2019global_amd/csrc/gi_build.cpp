@@ -563,6 +563,28 @@ void assign_plane_groups(HostScene& hs) {
 
 }  // namespace
 
+// The flat leaf table (gi_scene.h XFlatLeaf): every leaf child of every wide node once, its box the
+// node's own floats, with its xhot range and plane group.
+void build_xflat(HostScene& hs) {
+    hs.xflat.clear();
+    bool ok = true;
+    for (const XWNode& w : hs.xwnodes) {
+        const uint8_t* g = reinterpret_cast<const uint8_t*>(w.pad);
+        for (int c = 0; c < 8; ++c) {
+            if (w.child[c] >= 0 || w.child[c] == XEMPTY) continue;
+            XFlatLeaf f;
+            for (int k = 0; k < 3; ++k) { f.lo[k] = w.lo[k][c]; f.hi[k] = w.hi[k][c]; }
+            f.off = ~w.child[c];
+            f.cnt = w.cnt[c];
+            f.group = g[c];
+            f.pad = 0;
+            ok = ok && f.cnt <= 255 && f.off < 65536;
+            hs.xflat.push_back(f);
+        }
+    }
+    hs.x_flat_ok = ok && hs.xflat.size() <= (size_t)GI_XFLAT_MAX;
+}
+
 bool build_host_scene(const gi_scene_desc& desc, HostScene& hs, std::string& err) {
     std::vector<BEnt> ents((size_t)desc.n_entities);
     for (int i = 0; i < desc.n_entities; ++i)
@@ -670,6 +692,7 @@ bool build_host_scene(const gi_scene_desc& desc, HostScene& hs, std::string& err
         if (const char* lm = std::getenv("GI_XLEAF_MAX")) leaf_max = std::max(1, std::atoi(lm));
         build_xbvh(hs.xprims, bounds, leaf_max, hs, true);
         assign_plane_groups(hs);
+        build_xflat(hs);
         return true;
     }
     hs.xnodes.resize(1);
@@ -786,6 +809,7 @@ bool build_host_scene(const gi_scene_desc& desc, HostScene& hs, std::string& err
     }
     finalize_xwnodes(hs.xwnodes);
     assign_plane_groups(hs);
+    build_xflat(hs);
     return true;
 }
 

@@ -484,7 +484,7 @@ int scene_create_on(const gi_scene_desc* desc, int device, gi_scene** out) {
         (e = upload(sp, h.ents, &d.ents)) != hipSuccess || (e = upload(sp, h.tris, &d.tris)) != hipSuccess ||
         (e = upload(sp, h.xwnodes, &d.xwnodes)) != hipSuccess || (e = upload(sp, h.xhot, &d.xhot)) != hipSuccess ||
         (e = upload(sp, h.xbox, &d.xbox)) != hipSuccess ||
-        (e = upload(sp, h.xprims, &d.xprims)) != hipSuccess ||
+        (e = upload(sp, h.xprims, &d.xprims)) != hipSuccess || (e = upload(sp, h.xflat, &d.xflat)) != hipSuccess ||
         (e = upload(sp, std::vector<unsigned>(16, 0u), const_cast<const unsigned**>(&d.work))) != hipSuccess ||
         (e = upload(sp, h.app_off, &d.app_off)) != hipSuccess || (e = upload(sp, h.app_rec, &d.app_rec)) != hipSuccess ||
         (e = upload(sp, h.rpath_rec, &d.rpath_rec)) != hipSuccess || (e = upload(sp, h.rc_nodes, &d.rc_nodes)) != hipSuccess ||
@@ -509,6 +509,9 @@ int scene_create_on(const gi_scene_desc* desc, int device, gi_scene** out) {
         const size_t bytes = h.xwnodes.size() * sizeof(XWNode) + h.xhot.size() * sizeof(XHot) +
                              h.xprims.size() * sizeof(XPrim) + h.ents.size() * sizeof(REnt);
         d.x_lds_bytes = bytes <= 40 * 1024 ? (int32_t)bytes : 0;
+        // the flat leaf query (gi_wf.hip wf_flat): scenes staged in LDS whose leaf table fits
+        d.n_xflat = (int32_t)h.xflat.size();
+        d.x_flat = (d.x_lds_bytes > 0 && h.x_flat_ok) ? 1 : 0;
         // light shading (no acos texture mapping, no sphere primitives): 4 waves per SIMD pay off,
         // provided four workgroups fit a CU's 160 KB: each holds the scene, the per-lane path slots
         // (256 lanes x 80 B) and the per-wave unit blocks (4 x 68 x 4 B)

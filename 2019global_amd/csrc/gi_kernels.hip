@@ -2278,10 +2278,11 @@ long long shard_tiles(int w, int h, int shard_count) { return make_map(w, h, sha
 // of cheap background samples such as the main.cpp scene prefer 8).  The rest are TEST hooks that pick
 // among kernels whose frames are identical bit for bit (tests/test_gpu_parity.py compares them):
 // GI_X_WF (0/1/2: force a Mode X form for a whole suite run), GI_X_HELP=0 (no shadow-ray handoff),
+// GI_X_FLAT=0 (k_seg / k_wf_bounce walk the tree even where the scene's flat leaf table applies),
 // GI_R_FLAT (0/1/2: force a Mode R kernel), GI_RF_PER_SLOT (the flat Mode R pool size: 0 forces the
 // per-tile overflow path), GI_RF_GROUP (1/4: force k_rf_reach's lanes per hit).
 struct XEnv {
-    int run_log2 = 0, help = 1, wf = -1;
+    int run_log2 = 0, help = 1, wf = -1, flat = 1;
     int r_flat = -1;                  // Mode R kernels (GI_R_FLAT): 1 the flat phases for every scene, 0 k_mode_r
                                       // for every scene, 2 k_mode_r_batch for the whole frame (tests); -1 by size
     int rf_per_slot = 16;             // flat Mode R: pool pairs per pixel slot of the frame (GI_RF_PER_SLOT)
@@ -2292,6 +2293,7 @@ const XEnv& x_env() {
     static std::once_flag once;
     std::call_once(once, [] {
         if (const char* v = std::getenv("GI_X_HELP")) env.help = std::atoi(v) != 0;
+        if (const char* v = std::getenv("GI_X_FLAT")) env.flat = std::atoi(v) != 0;
         if (const char* v = std::getenv("GI_R_FLAT")) env.r_flat = std::atoi(v);
         if (const char* v = std::getenv("GI_RF_PER_SLOT")) env.rf_per_slot = std::max(0, std::min(1024, std::atoi(v)));
         if (const char* v = std::getenv("GI_X_WF")) env.wf = std::atoi(v);
@@ -2310,7 +2312,7 @@ hipError_t launch_wf(const DevScene& sc, int kv, size_t lds_bytes, int resident,
                      int w, int h, int y0, const gi_opts& o, double* rgb, uint8_t* rgb8, const XScratch& xs,
                      const unsigned* n_list_dev, unsigned long long* stats, int xflags, hipStream_t stream,
                      hipEvent_t ev_begin, hipEvent_t ev_end);
-hipError_t wf_occupancy(const DevScene& sc, int kv, size_t lds_bytes, int form, int* per_cu);
+hipError_t wf_occupancy(const DevScene& sc, int kv, bool flat, size_t lds_bytes, int form, int* per_cu);
 size_t wf_slot_bytes();
 size_t wf_scene_lds_bytes(const DevScene& sc);
 
@@ -2372,10 +2374,11 @@ hipError_t x_launch_config(const DevScene& sc, int device, XLaunchCfg& cfg) {
     if (e != hipSuccess) return e;
     cfg.resident = std::max(1, cus) * std::max(1, per_cu);
     cfg.wf_lds_bytes = (lds ? wf_scene_lds_bytes(sc) : 16 * 256 * sizeof(int)) + wf_slot_bytes();
-    e = wf_occupancy(sc, cfg.kv, cfg.wf_lds_bytes, 1, &per_cu);
+    const bool flat = sc.x_flat && x_env().flat;   // (the launches' choice: launch_render's bit 6)
+    e = wf_occupancy(sc, cfg.kv, flat, cfg.wf_lds_bytes, 1, &per_cu);
     if (e != hipSuccess) return e;
     cfg.wf_resident = std::max(1, cus) * std::max(1, per_cu);
-    e = wf_occupancy(sc, cfg.kv, cfg.wf_lds_bytes, 2, &per_cu);
+    e = wf_occupancy(sc, cfg.kv, flat, cfg.wf_lds_bytes, 2, &per_cu);
     if (e != hipSuccess) return e;
     cfg.seg_resident = std::max(1, cus) * std::max(1, per_cu);
     return hipSuccess;
@@ -2488,10 +2491,11 @@ hipError_t launch_render(const DevScene& sc, const XLaunchCfg& xc, const CamDev&
         // estimate for the scene (DevScene::x_handle8)
         const int h8 = sc.x_handle8;
         // schedule flags (bit 0: inline shadow, bit 2: no shadow rays, bit 3: shadow handoff, bit 4:
-        // spread work groups -- with the handoff build, bit 5: pixel-major work blocks) and the
-        // maximum run length (log2, bits 8-10)
+        // spread work groups -- with the handoff build, bit 5: pixel-major work blocks, bit 6: gi_wf.hip's
+        // forms walk the tree although the flat leaf table applies, GI_X_FLAT=0) and the maximum run
+        // length (log2, bits 8-10)
         const int xf = sc.x_flags | (env.run_log2 << 8) | ((o.flags & GI_FLAG_X_NO_SHADOW) ? 4 : 0) | (env.help ? 8 : 0) |
-                       (help ? 16 : 0) | 32;
+                       (help ? 16 : 0) | 32 | (env.flat ? 0 : 64);
         if (form) {   // gi_wf.hip's forms, timed as one pass
             if (!xs.wcnt || (form == 1 && (!xs.wq[0] || !xs.wq[1] || xs.wcap <= 0))) return hipErrorInvalidValue;
             e = launch_wf(sc, xc.kv, xc.wf_lds_bytes, form == 2 ? xc.seg_resident : xc.wf_resident, form, cam, light, w, h, y0,

@@ -129,6 +129,21 @@ static_assert(sizeof(XBox) == 32, "XBox layout");
 struct XLeaf {
     int32_t off, cnt;      // host build only: range in xprim_idx
 };
+// Flat leaf table (build_xflat; gi_wf.hip wf_flat): one record per leaf child of the wide tree, in
+// node order then child order.  lo / hi are the very floats of the child's XWNode box, so the
+// proof that those padded boxes are conservative covers the table too.
+#ifndef GI_XFLAT_MAX
+#define GI_XFLAT_MAX 32    // most leaves of a scene that answers its queries from the table
+#endif
+static_assert(GI_XFLAT_MAX >= 1 && GI_XFLAT_MAX <= 32, "the candidate mask is one 32-bit word");
+struct XFlatLeaf {         // 32 bytes
+    float lo[3], hi[3];
+    int32_t off;           // the leaf's first record in xhot[]
+    uint16_t cnt;          // its records
+    uint8_t group;         // its plane group (byte c of XWNode::pad; 255 none)
+    uint8_t pad;
+};
+static_assert(sizeof(XFlatLeaf) == 32, "XFlatLeaf layout");
 
 struct HostScene {
     // Mode R
@@ -167,7 +182,12 @@ struct HostScene {
     double x_est_nodes = 0, x_est_prims = 0;   // SAH estimates per random ray through the root
     bool x_spatial = false;  // the Mode X BVH was built with spatial splits (a primitive in several leaves)
     double x_skip_a = 0.0, x_skip_b = 2.0;   // own-plane leaf skip: |d . n| >= a * max|cam| + b (gi_build.cpp)
+    std::vector<XFlatLeaf> xflat;    // the wide tree's leaf children (build_xflat)
+    bool x_flat_ok = false;          // xflat fits the flat query: <= GI_XFLAT_MAX leaves of <= 255 records each,
+                                     // offsets below 2^16 (wf_flat packs offset, index and count in a word)
 };
+// Fills hs.xflat / x_flat_ok from hs.xwnodes (after assign_plane_groups: the group bytes are copied).
+void build_xflat(HostScene& hs);
 
 // Sets XWNode::exists from the child references (both Mode X builders call it last).
 inline void finalize_xwnodes(std::vector<XWNode>& w) {
@@ -222,6 +242,10 @@ struct DevScene {
     const int32_t* r_leaf_of_rank;
     int32_t n_r_always;
     float rc_ext;
+    // Mode X flat leaf table (HostScene::xflat), read through the constant cache at wave-uniform addresses
+    const XFlatLeaf* xflat;
+    int32_t n_xflat;
+    int32_t x_flat;        // 1: the scene is staged in LDS and its table fits (k_seg / k_wf_bounce use wf_flat)
 };
 
 // HIP events bracketing the dominant kernel of renders issued with GI_FLAG_TIME (owned by the

@@ -185,6 +185,167 @@ __device__ __forceinline__ int wf_trace(NodeP W, HotP H, V3 o, V3 d, double tmax
     return best;
 }
 
+// The flat leaf query (scenes staged in LDS with at most GI_XFLAT_MAX leaves): the same
+// answer as wf_trace without the tree walk.
+//  Phase A, uniform over the wave: every record of the leaf table (DevScene::xflat) is read at a
+//    wave-uniform address -- through the constant cache, so its eight words are scalar operands -- and
+//    its box tested for every lane with child_hit's arithmetic against [0, tmax]; leaves of the ray's
+//    own plane group are dropped as children_mask<AXIS, true> drops them.  Hit leaves set their bit in
+//    the lane's candidate mask.  Closest hit: the nearest candidate (entry distance tn1) and the second
+//    smallest entry distance tn2 are kept.  Any hit: the last candidate found.
+//  Phase B, per lane: the PAIR leaf block of wf_trace on one candidate per iteration.  Closest hit:
+//    the nearest candidate first; a lane whose best t lies in front of tn2 is finished (no other box
+//    reaches it); otherwise the remaining candidates in bit order, each re-tested against the current
+//    best t (a per-lane read of its record) before its exact tests.  Any hit: candidates from the
+//    highest bit down until one is hit.
+// Exactness: the closest hit is the (t, primitive) minimum over all primitives whatever the order,
+// a leaf is left out only by the conservative box test or the own-plane rule the tree walk uses,
+// and the shadow answer is a boolean.
+// STATS: nnode counts the 256-byte units of the table a query reads, nsteps Phase B's iterations.
+#ifndef GI_XFLAT_CHUNK
+#define GI_XFLAT_CHUNK 0
+#endif
+#ifndef GI_XFLAT_UNROLL
+#define GI_XFLAT_UNROLL 4   // Phase A records in flight (their loads overlap the previous records' tests)
+#endif
+typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
+#ifndef GI_XFLAT_LDS
+#define GI_XFLAT_LDS 0   // (A/B builds) 1: phase A reads a copy of the table staged in LDS, a broadcast read per record
+#endif
+// record k's eight words from the constant address space: a scalar load at a uniform address
+__device__ __forceinline__ u32x8 flat_rec_uniform(const XFlatLeaf* tab, int k) {
+#if GI_XFLAT_LDS
+    const int4* q = reinterpret_cast<const int4*>(tab + k);
+    const int4 a = q[0], b = q[1];
+    return u32x8{(uint32_t)a.x, (uint32_t)a.y, (uint32_t)a.z, (uint32_t)a.w, (uint32_t)b.x, (uint32_t)b.y, (uint32_t)b.z, (uint32_t)b.w};
+#else
+    return *(const __attribute__((address_space(4))) u32x8*)(uintptr_t)(tab + k);
+#endif
+}
+// (offset, index, count) of a candidate in one word: offset < 2^16, count <= 255 (HostScene::x_flat_ok)
+__device__ __forceinline__ uint32_t flat_pack(uint32_t off, int k, uint32_t w7) { return off | ((uint32_t)k << 16) | ((w7 & 0xFFu) << 24); }
+// child_hit on a table record read per lane
+__device__ __forceinline__ bool flat_hit(const XFlatLeaf* r, F3 no, F3 ivf, int sm, float tmax, uint32_t& pk, int k) {
+    const int4* q = reinterpret_cast<const int4*>(r);
+    const int4 a = q[0], b = q[1];
+    const float lx = __int_as_float(a.x), ly = __int_as_float(a.y), lz = __int_as_float(a.z);
+    const float hx = __int_as_float(a.w), hy = __int_as_float(b.x), hz = __int_as_float(b.y);
+    const float nx = (sm & 1) ? hx : lx, fx = (sm & 1) ? lx : hx;
+    const float ny = (sm & 2) ? hy : ly, fy = (sm & 2) ? ly : hy;
+    const float nz = (sm & 4) ? hz : lz, fz = (sm & 4) ? lz : hz;
+    const float tn = fmaxf(fmaxf(__builtin_fmaf(nx, ivf.x, no.x), __builtin_fmaf(ny, ivf.y, no.y)),
+                           fmaxf(__builtin_fmaf(nz, ivf.z, no.z), 0.0f));
+    const float tf = fminf(fminf(__builtin_fmaf(fx, ivf.x, no.x), __builtin_fmaf(fy, ivf.y, no.y)),
+                           fminf(__builtin_fmaf(fz, ivf.z, no.z), tmax));
+    pk = flat_pack((uint32_t)b.z, k, (uint32_t)b.w);
+    return tn <= tf;
+}
+template <bool ANY, bool TRI>
+__device__ __forceinline__ int wf_flat(const XFlatLeaf* tab, int n, const XHot* H, V3 o, V3 d, double tmax, bool act,
+                                       double& t_out, uint32_t& nnode, uint32_t& nprim, uint32_t& nsteps, int skip) {
+    const F3 of = f3((float)o.x, (float)o.y, (float)o.z);
+    const F3 ivf = inv_dir(d);
+    const F3 no = neg_oiv(of, ivf);
+    const int sm = iv_signs(ivf);
+    const bool sx = (sm & 1) != 0, sy = (sm & 2) != 0, sz = (sm & 4) != 0;
+    double tb = tmax;
+    float tbf = up32(tmax);
+    int best = -1;
+    // ---- phase A (a lane without a ray: an empty interval, no candidates)
+    const float tfa = act ? tbf : -1.0f;
+    uint32_t m = 0, pk = 0;
+    float tn1 = INFINITY, tn2 = INFINITY;
+    auto step = [&](const u32x8 w, int k) {
+        const float lx = __uint_as_float(w[0]), ly = __uint_as_float(w[1]), lz = __uint_as_float(w[2]);
+        const float hx = __uint_as_float(w[3]), hy = __uint_as_float(w[4]), hz = __uint_as_float(w[5]);
+        // both planes' distances, then near / far by the reciprocal's sign: child_hit's values (the
+        // planes are scalar operands, so the choice is made on the products)
+        const float ax = __builtin_fmaf(lx, ivf.x, no.x), bx = __builtin_fmaf(hx, ivf.x, no.x);
+        const float ay = __builtin_fmaf(ly, ivf.y, no.y), by = __builtin_fmaf(hy, ivf.y, no.y);
+        const float az = __builtin_fmaf(lz, ivf.z, no.z), bz = __builtin_fmaf(hz, ivf.z, no.z);
+        const float tn = fmaxf(fmaxf(sx ? bx : ax, sy ? by : ay), fmaxf(sz ? bz : az, 0.0f));
+        const float tf = fminf(fminf(sx ? ax : bx, sy ? ay : by), fminf(sz ? az : bz, tfa));
+        const bool hit = (tn <= tf) & ((int)((w[7] >> 16) & 0xFFu) != skip);
+        const uint32_t pkk = flat_pack(w[6], k, w[7]);
+        m |= hit ? 1u << k : 0u;
+        if (ANY) {
+            pk = hit ? pkk : pk;
+        } else {
+            const float th = hit ? tn : INFINITY;
+            pk = th < tn1 ? pkk : pk;
+            tn2 = __builtin_amdgcn_fmed3f(tn1, tn2, th);   // (tn1 <= tn2: the middle is the second smallest)
+            tn1 = fminf(tn1, th);
+        }
+    };
+    int k0 = 0;
+#if GI_XFLAT_CHUNK
+    for (; k0 + 4 <= n; k0 += 4) {   // four records' loads in flight, then their tests
+        const u32x8 w0 = flat_rec_uniform(tab, k0), w1 = flat_rec_uniform(tab, k0 + 1);
+        const u32x8 w2 = flat_rec_uniform(tab, k0 + 2), w3 = flat_rec_uniform(tab, k0 + 3);
+        step(w0, k0);
+        step(w1, k0 + 1);
+        step(w2, k0 + 2);
+        step(w3, k0 + 3);
+    }
+#pragma unroll 1
+#else
+#pragma unroll GI_XFLAT_UNROLL
+#endif
+    for (int k = k0; k < n; ++k) step(flat_rec_uniform(tab, k), k);
+    if (act) nnode += (uint32_t)((n * (int)sizeof(XFlatLeaf) + 255) / 256);
+    // ---- phase B
+    bool go = m != 0;
+    if (go) m &= ~(1u << ((pk >> 16) & 0xFFu));
+    while (go) {
+        ++nsteps;
+        const int cnt = (int)(pk >> 24);
+        const XHot* hp = H + (pk & 0xFFFFu);
+        for (int j = 0; j < cnt; j += 2) {
+            const bool two = j + 1 < cnt;
+            const XHotR r0 = load_hot(hp + j), r1 = load_hot(hp + (two ? j + 1 : j));
+            const double ta = x_prim_t<TRI>(r0.h, o, d, MX_TMIN);
+            const double tq = two ? x_prim_t<TRI>(r1.h, o, d, MX_TMIN) : INFINITY;
+            nprim += two ? 2 : 1;
+            if (ANY) {
+                if ((ta < tmax) | (tq < tmax)) {
+                    best = ta < tmax ? r0.h.prim : r1.h.prim;
+                    break;
+                }
+            } else {   // (selects, not branches: | and & do not short-circuit)
+                const bool ua = (ta < tb) | ((ta == tb) & (r0.h.prim < best));
+                tb = ua ? ta : tb;
+                best = ua ? r0.h.prim : best;
+                const bool uq = (tq < tb) | ((tq == tb) & (r1.h.prim < best));
+                tb = uq ? tq : tb;
+                best = uq ? r1.h.prim : best;
+                tbf = up32(tb);
+            }
+        }
+        go = false;
+        if (ANY) {
+            if (best < 0 && m != 0) {
+                const int k = 31 - __builtin_clz(m);
+                m &= ~(1u << k);
+                const int4 b = reinterpret_cast<const int4*>(tab + k)[1];
+                pk = flat_pack((uint32_t)b.z, k, (uint32_t)b.w);
+                go = true;
+            }
+        } else {
+            if (tn2 > tbf) m = 0;   // every other candidate's box begins behind the best t
+            while (m != 0) {
+                const int k = __builtin_ctz(m);
+                m &= m - 1;
+                if (flat_hit(tab + k, no, ivf, sm, tbf, pk, k)) {
+                    go = true;
+                    break;
+                }
+            }
+        }
+    }
+    t_out = tb;
+    return best;
+}
+
 struct WFArgs {
     const unsigned* list;      // k_x_classify's work list (pixel slots, tile order)
     const unsigned* n_list;    // its length (device)
@@ -204,6 +365,7 @@ struct WFView {
     const XHot* LH = nullptr;
     const XPrim* XP = nullptr;
     const REnt* EN = nullptr;
+    const XFlatLeaf* FT = nullptr;   // the flat leaf table phase A reads
     int* nst = nullptr;
     double* pl = nullptr;   // this lane's L (fields 0-2) and T (3-5), pl[f * 256]
 };
@@ -212,6 +374,7 @@ __device__ __forceinline__ WFView wf_stage(const DevScene& sc, int4* lds_dyn) {
     WFView v;
     v.XP = sc.xprims;
     v.EN = sc.ents;
+    v.FT = sc.xflat;
     if constexpr (LDS) {
         const int nw = sc.n_xwnodes * (int)(sizeof(XWNode) / sizeof(int4));
         const int nh = sc.n_xhot * (int)(sizeof(XHot) / sizeof(int4));
@@ -225,12 +388,20 @@ __device__ __forceinline__ WFView wf_stage(const DevScene& sc, int4* lds_dyn) {
         for (int i = threadIdx.x; i < nh; i += blockDim.x) lds_dyn[nw + i] = gh[i];
         for (int i = threadIdx.x; i < np; i += blockDim.x) lds_dyn[nw + nh + i] = gp[i];
         for (int i = threadIdx.x; i < ne; i += blockDim.x) lds_dyn[nw + nh + np + i] = ge[i];
+#if GI_XFLAT_LDS
+        const int nf = sc.n_xflat * (int)(sizeof(XFlatLeaf) / sizeof(int4));
+        const int4* gf = reinterpret_cast<const int4*>(sc.xflat);
+        for (int i = threadIdx.x; i < nf; i += blockDim.x) lds_dyn[nw + nh + np + ne + i] = gf[i];
+        v.FT = reinterpret_cast<const XFlatLeaf*>(lds_dyn + nw + nh + np + ne);
+#else
+        const int nf = 0;
+#endif
         __syncthreads();
         v.LW = reinterpret_cast<const XWNode*>(lds_dyn);
         v.LH = reinterpret_cast<const XHot*>(lds_dyn + nw);
         v.XP = reinterpret_cast<const XPrim*>(lds_dyn + nw + nh);
         v.EN = reinterpret_cast<const REnt*>(lds_dyn + nw + nh + np);
-        v.pl = reinterpret_cast<double*>(lds_dyn + nw + nh + np + ne) + threadIdx.x;
+        v.pl = reinterpret_cast<double*>(lds_dyn + nw + nh + np + ne + nf) + threadIdx.x;
     } else {
         v.nst = reinterpret_cast<int*>(lds_dyn) + threadIdx.x;   // 16 levels x 256 lanes
         v.pl = reinterpret_cast<double*>(reinterpret_cast<int*>(lds_dyn) + 16 * 256) + threadIdx.x;
@@ -294,7 +465,7 @@ __device__ __forceinline__ void wf_wave_steps(uint32_t n, uint64_t& it, uint64_t
     }
     if ((threadIdx.x & 63) == 0) { it += mx; ln += sm; }
 }
-template <bool STATS, bool LDS, bool SH, bool TRI, bool CN, typename KeyF>
+template <bool STATS, bool LDS, bool SH, bool TRI, bool CN, bool FLAT, typename KeyF>
 __device__ __forceinline__ bool x_segment(const DevScene& sc, const WFView& v, const V3& light, int depth, bool no_shadow, bool act,
                                           const KeyF& id_of, V3& o, V3& d, V3& L, V3& T,
                                           uint32_t& nnode, uint32_t& nprim, uint32_t& nrays, WFSegStats& ws,
@@ -308,7 +479,8 @@ __device__ __forceinline__ bool x_segment(const DevScene& sc, const WFView& v, c
     int best;
     // the own-plane skip of this ray (k_seg carries it from the previous segment; 254: none)
     const int skip_c = splane ? *splane : 254;
-    if constexpr (LDS) best = wf_trace<false, true, false, SH, TRI, false>(v.LW, v.LH, o, d, INFINITY, act, v.nst, tbest, nnode, nprim, st_steps, skip_c);
+    if constexpr (FLAT) best = wf_flat<false, TRI>(v.FT, sc.n_xflat, v.LH, o, d, INFINITY, act, tbest, nnode, nprim, st_steps, skip_c);
+    else if constexpr (LDS) best = wf_trace<false, true, false, SH, TRI, false>(v.LW, v.LH, o, d, INFINITY, act, v.nst, tbest, nnode, nprim, st_steps, skip_c);
     else if constexpr (CN) best = wf_trace<false, false, false, SH, TRI, true>(sc.xcnodes, sc.xhot, o, d, INFINITY, act, v.nst, tbest, nnode, nprim, st_steps);
     else best = wf_trace<false, false, false, SH, TRI, true>(sc.xwnodes, sc.xhot, o, d, INFINITY, act, v.nst, tbest, nnode, nprim, st_steps, skip_c);
     if (act) ++nrays;
@@ -337,7 +509,8 @@ __device__ __forceinline__ bool x_segment(const DevScene& sc, const WFView& v, c
         double tdummy;
         int sb;
         const int skip_s = (pg < 254 && fabs(dot(Ld, pn)) >= skip_cos) ? pg : 254;
-        if constexpr (LDS) sb = wf_trace<true, true, false, SH, TRI, false>(v.LW, v.LH, P, Ld, ldist, hit, v.nst, tdummy, nnode, nprim, st_steps, skip_s);
+        if constexpr (FLAT) sb = wf_flat<true, TRI>(v.FT, sc.n_xflat, v.LH, P, Ld, ldist, hit, tdummy, nnode, nprim, st_steps, skip_s);
+        else if constexpr (LDS) sb = wf_trace<true, true, false, SH, TRI, false>(v.LW, v.LH, P, Ld, ldist, hit, v.nst, tdummy, nnode, nprim, st_steps, skip_s);
         else if constexpr (CN) sb = wf_trace<true, false, false, SH, TRI, true>(sc.xcnodes, sc.xhot, P, Ld, ldist, hit, v.nst, tdummy, nnode, nprim, st_steps);
         else sb = wf_trace<true, false, false, SH, TRI, true>(sc.xwnodes, sc.xhot, P, Ld, ldist, hit, v.nst, tdummy, nnode, nprim, st_steps, skip_s);
         occl = sb >= 0;
@@ -410,7 +583,7 @@ __device__ __forceinline__ bool x_segment(const DevScene& sc, const WFView& v, c
 
 // One bounce of every live path (the wavefront form).  Persistent grid: each wave takes GI_WF_TAKE
 // batches of 64 queue entries per atomic until the queue is exhausted.
-template <bool STATS, bool LDS, bool W4, bool SH, bool TRI, bool CN>
+template <bool STATS, bool LDS, bool W4, bool SH, bool TRI, bool CN, bool FLAT>
 __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_WAVES) void k_wf_bounce(
     DevScene sc, CamDev cam, V3 light, TileMap m, int spp, int depth, uint64_t seed, int b, double* rgb, uint8_t* rgb8,
     unsigned long long* stats, WFArgs a, WFQ qin, WFQ qout, int xflags) {
@@ -487,7 +660,7 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
         // (the queue carries no plane: the closest ray is not skipped here, the shadow ray is)
         const double skip_cos = sc.x_skip_a * fmax(fabs(cam.pos.x), fmax(fabs(cam.pos.y), fabs(cam.pos.z))) + sc.x_skip_b;
         int splane = 254;
-        const bool cont = x_segment<false, LDS, SH, TRI, CN>(sc, v, light, depth, no_shadow, act, [&] { return PathId{key, smp, b}; }, o, d, L, T,
+        const bool cont = x_segment<false, LDS, SH, TRI, CN, FLAT>(sc, v, light, depth, no_shadow, act, [&] { return PathId{key, smp, b}; }, o, d, L, T,
                                                              nnode, nprim, nrays, ws, skip_cos, &splane);
         // ---- live paths to the next bounce's queue: one atomic per wave, entries in lane order
         const unsigned long long mc = __ballot(cont);
@@ -531,7 +704,7 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
 #ifndef GI_SEG_TAKE_TRI
 #define GI_SEG_TAKE_TRI 1   // the same for LDS-resident triangle-only scenes (the Cornell box)
 #endif
-template <bool STATS, bool LDS, bool W4, bool SH, bool TRI, bool CN>
+template <bool STATS, bool LDS, bool W4, bool SH, bool TRI, bool CN, bool FLAT>
 __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_WAVES) void k_seg(
     DevScene sc, CamDev cam, V3 light, TileMap m, int spp, int depth, uint64_t seed, double* rgb, uint8_t* rgb8,
     unsigned long long* stats, WFArgs a, int xflags) {
@@ -642,7 +815,7 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
             const unsigned long long ml = __ballot(live);
             if (lane == 0) { ++ws.segs; ws.live += __popcll(ml); }
         }
-        const bool cont = x_segment<STATS, LDS, SH, TRI, CN>(
+        const bool cont = x_segment<STATS, LDS, SH, TRI, CN, FLAT>(
             sc, v, light, depth, no_shadow, live,
             [&] { return PathId{slot_get_u64(v.pl, 6), (unsigned)(slot_get_u64(v.pl, 7) >> 32), (int)slot_get_u64(v.pl, 8)}; },
             o, d, L, T, nnode, nprim, nrays, ws, skip_cos, &splane);
@@ -685,34 +858,37 @@ size_t wf_slot_bytes() { return kWfSlotBytes; }
 // the scene's share of that LDS (LDS-resident scenes): the staged records (entity records included:
 // read from global memory by the shading instead, C3 4.65 -> 4.69 ms, and 5 waves per SIMD with them
 // there, 96 VGPRs and 120 B of scratch, 4.79 ms; profiles/r06_ab.txt)
-size_t wf_scene_lds_bytes(const DevScene& sc) { return (size_t)sc.x_lds_bytes; }
+size_t wf_scene_lds_bytes(const DevScene& sc) { return (size_t)sc.x_lds_bytes + (GI_XFLAT_LDS ? (size_t)sc.n_xflat * sizeof(XFlatLeaf) : 0); }
 
-// The kernel variant for a scene: f(LDS, W4, SH, TRI, CN) with each a std::integral_constant<bool>
-// (kv: 2 * LDS-resident + light-shading, XLaunchCfg::kv)
+// The kernel variant for a scene: f(LDS, W4, SH, TRI, CN, FLAT) with each a std::integral_constant<bool>
+// (kv: 2 * LDS-resident + light-shading, XLaunchCfg::kv; flat: the flat leaf query, LDS-resident scenes
+// whose table applies -- DevScene::x_flat -- unless GI_X_FLAT=0)
 template <typename F>
-void wf_dispatch(const DevScene& sc, int kv, F&& f) {
+void wf_dispatch(const DevScene& sc, int kv, bool flat, F&& f) {
     using B = std::true_type;
     using N = std::false_type;
     const bool lds = kv >= 2, w4 = kv == 3, sh = sc.x_max_depth <= 7, tr = sc.x_tri_only != 0;
     const bool cn = !lds && sc.xcnodes != nullptr;
-    if (lds) {
-        if (w4) { if (sh) f(B{}, B{}, B{}, B{}, N{}); else f(B{}, B{}, N{}, B{}, N{}); }
-        else { if (sh) f(B{}, N{}, B{}, N{}, N{}); else f(B{}, N{}, N{}, N{}, N{}); }
+    if (lds && flat && sc.x_flat) {   // (SH only shapes the tree walk's level masks: one flat kernel per W4)
+        if (w4) f(B{}, B{}, B{}, B{}, N{}, B{}); else f(B{}, N{}, B{}, N{}, N{}, B{});
+    } else if (lds) {
+        if (w4) { if (sh) f(B{}, B{}, B{}, B{}, N{}, N{}); else f(B{}, B{}, N{}, B{}, N{}, N{}); }
+        else { if (sh) f(B{}, N{}, B{}, N{}, N{}, N{}); else f(B{}, N{}, N{}, N{}, N{}, N{}); }
     } else if (cn) {
-        if (tr) f(N{}, N{}, N{}, B{}, B{}); else f(N{}, N{}, N{}, N{}, B{});
+        if (tr) f(N{}, N{}, N{}, B{}, B{}, N{}); else f(N{}, N{}, N{}, N{}, B{}, N{});
     } else {
-        if (tr) f(N{}, N{}, N{}, B{}, N{}); else f(N{}, N{}, N{}, N{}, N{});
+        if (tr) f(N{}, N{}, N{}, B{}, N{}, N{}); else f(N{}, N{}, N{}, N{}, N{}, N{});
     }
 }
 
 // resident workgroups per CU of the kernel a form (1: k_wf_bounce, 2: k_seg) runs for this scene
-hipError_t wf_occupancy(const DevScene& sc, int kv, size_t lds_bytes, int form, int* per_cu) {
+hipError_t wf_occupancy(const DevScene& sc, int kv, bool flat, size_t lds_bytes, int form, int* per_cu) {
     hipError_t e = hipSuccess;
-    wf_dispatch(sc, kv, [&](auto L, auto W, auto SHt, auto T, auto C) {
+    wf_dispatch(sc, kv, flat, [&](auto L, auto W, auto SHt, auto T, auto C, auto FL) {
         constexpr bool l = decltype(L)::value, w = decltype(W)::value, sh = decltype(SHt)::value,
-                       t = decltype(T)::value, c = decltype(C)::value;
-        const void* f = form == 2 ? reinterpret_cast<const void*>(k_seg<false, l, w, sh, t, c>)
-                                  : reinterpret_cast<const void*>(k_wf_bounce<false, l, w, sh, t, c>);
+                       t = decltype(T)::value, c = decltype(C)::value, fl = decltype(FL)::value;
+        const void* f = form == 2 ? reinterpret_cast<const void*>(k_seg<false, l, w, sh, t, c, fl>)
+                                  : reinterpret_cast<const void*>(k_wf_bounce<false, l, w, sh, t, c, fl>);
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, f, 256, lds_bytes);
     });
     return e;
@@ -732,6 +908,7 @@ hipError_t launch_wf(const DevScene& sc, int kv, size_t lds_bytes, int resident,
     const int s0 = o.sample_end > 0 ? o.sample_begin : 0, s1 = o.sample_end > 0 ? o.sample_end : o.spp;
     const dim3 grid((unsigned)std::max(1, resident)), block(256);
     hipError_t e = hipSuccess;
+    const bool flat = (xflags & 64) == 0;   // (bit 6: GI_X_FLAT=0)
     if (form == 2) {   // (the unit counter xs.wcnt[0..1] was zeroed by k_x_classify)
         WFArgs a{};
         a.list = xs.list;
@@ -741,11 +918,11 @@ hipError_t launch_wf(const DevScene& sc, int kv, size_t lds_bytes, int resident,
         a.s0 = (unsigned)s0;
         a.ns = (unsigned)(s1 - s0);
         if (ev_begin) (void)hipEventRecord(ev_begin, stream);
-        wf_dispatch(sc, kv, [&](auto L, auto W, auto SHt, auto T, auto C) {
+        wf_dispatch(sc, kv, flat, [&](auto L, auto W, auto SHt, auto T, auto C, auto FL) {
             constexpr bool l = decltype(L)::value, wv = decltype(W)::value, sh = decltype(SHt)::value,
-                           t = decltype(T)::value, c = decltype(C)::value;
-            if (stats) hipLaunchKernelGGL((k_seg<true, l, wv, sh, t, c>), grid, block, lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, rgb, rgb8, stats, a, xflags);
-            else hipLaunchKernelGGL((k_seg<false, l, wv, sh, t, c>), grid, block, lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, rgb, rgb8, stats, a, xflags);
+                           t = decltype(T)::value, c = decltype(C)::value, fl = decltype(FL)::value;
+            if (stats) hipLaunchKernelGGL((k_seg<true, l, wv, sh, t, c, fl>), grid, block, lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, rgb, rgb8, stats, a, xflags);
+            else hipLaunchKernelGGL((k_seg<false, l, wv, sh, t, c, fl>), grid, block, lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, rgb, rgb8, stats, a, xflags);
         });
         if (ev_end) (void)hipEventRecord(ev_end, stream);
         return hipGetLastError();
@@ -777,11 +954,11 @@ hipError_t launch_wf(const DevScene& sc, int kv, size_t lds_bytes, int resident,
             qin.id = reinterpret_cast<uint2*>(xs.wid[(b + 1) & 1]);
             qout.r = xs.wq[b & 1];
             qout.id = reinterpret_cast<uint2*>(xs.wid[b & 1]);
-            wf_dispatch(sc, kv, [&](auto L, auto W, auto SHt, auto T, auto C) {
+            wf_dispatch(sc, kv, flat, [&](auto L, auto W, auto SHt, auto T, auto C, auto FL) {
                 constexpr bool l = decltype(L)::value, wv = decltype(W)::value, sh = decltype(SHt)::value,
-                               t = decltype(T)::value, c = decltype(C)::value;
-                if (stats) hipLaunchKernelGGL((k_wf_bounce<true, l, wv, sh, t, c>), grid, block, lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, b, rgb, rgb8, stats, a, qin, qout, xflags);
-                else hipLaunchKernelGGL((k_wf_bounce<false, l, wv, sh, t, c>), grid, block, lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, b, rgb, rgb8, stats, a, qin, qout, xflags);
+                               t = decltype(T)::value, c = decltype(C)::value, fl = decltype(FL)::value;
+                if (stats) hipLaunchKernelGGL((k_wf_bounce<true, l, wv, sh, t, c, fl>), grid, block, lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, b, rgb, rgb8, stats, a, qin, qout, xflags);
+                else hipLaunchKernelGGL((k_wf_bounce<false, l, wv, sh, t, c, fl>), grid, block, lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, b, rgb, rgb8, stats, a, qin, qout, xflags);
             });
         }
     }

@@ -149,7 +149,9 @@ typedef struct gi_opts {
 
 /* stats[] slots */
 #define GI_STAT_RAYS 0        /* rays traced (primary + bounce + shadow) */
-#define GI_STAT_NODES 1       /* octree node records fetched & tested */
+#define GI_STAT_NODES 1       /* octree node records fetched & tested; Mode X queries answered from the flat
+                                 leaf table (small LDS-resident scenes): the 256-byte units of table a
+                                 query reads, so nodes x the node size stays a byte count */
 #define GI_STAT_PRIMS 2       /* primitive records fetched & tested in fp64 */
 #define GI_STAT_PIXELS 3
 #define GI_STAT_X_PATH_MAX 4  /* Mode X: the longest sample path (primary ray to its end), a maximum:
