@@ -50,6 +50,7 @@ FLAG_X_NO_SHADOW = 8   # Mode X, tests only: no shadow rays (reduces depth-1 Mod
 FLAG_X_WF = 16   # Mode X: the wavefront form (one launch per bounce over compacted path queues, gi_wf.hip)
 FLAG_X_MEGA = 32   # Mode X: the persistent path-state kernel k_mode_x
 FLAG_X_SEG = 64   # Mode X: the segment-synchronous persistent form k_seg (no form flag: chosen per launch)
+KAT_X_TREE, KAT_X_HBM = 1, 2   # gi_kat_x_query's flags
 X_FORMS = ("k_mode_x", "k_wf_bounce", "k_seg")   # gi_scene_x_form's values
 R_KERNELS = ("k_mode_r", "k_rf_walk", "k_mode_r_batch")   # gi_scene_r_kernel's (1: the flat phases)
 STAT_RAYS, STAT_NODES, STAT_PRIMS, STAT_PIXELS, STAT_X_PATH_MAX = 0, 1, 2, 3, 4
@@ -61,7 +62,7 @@ STAT_X_IT_RS, STAT_X_LN_RS, STAT_X_IT_ST, STAT_X_LN_ST = 20, 21, 22, 23
 STAT_R_PAIRS, STAT_R_OVF_TILES = 24, 25
 STATS_N = 26
 TILE = 8
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class GIError(RuntimeError):
@@ -109,7 +110,7 @@ TILE_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ct
 
 EXPORTS = ["gi_abi_version", "gi_last_error", "gi_camera_init", "gi_scene_create", "gi_scene_destroy",
            "gi_scene_get_info", "gi_render", "gi_render_device", "gi_shard_tiles", "gi_unshard_device",
-           "gi_trace_ray", "gi_kat_expbox", "gi_scene_kernel_ms", "gi_scene_x_form", "gi_scene_r_kernel", "gi_octree_create", "gi_octree_destroy",
+           "gi_trace_ray", "gi_kat_expbox", "gi_kat_x_query", "gi_kat_x_variant", "gi_scene_kernel_ms", "gi_scene_x_form", "gi_scene_r_kernel", "gi_octree_create", "gi_octree_destroy",
            "gi_octree_intersect", "gi_multi_create", "gi_multi_destroy", "gi_multi_info", "gi_multi_render", "gi_device_count",
            "gi_device_list", "gi_build_id", "gi_obj_parse"]
 
@@ -147,6 +148,9 @@ def lib():
         L.gi_unshard_device.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp]
         L.gi_trace_ray.argtypes = [vp, dp, dp, dp, ctypes.POINTER(Hit), dp]
         L.gi_kat_expbox.argtypes = [i32, dp, ctypes.POINTER(ctypes.c_int32)]
+        ip = ctypes.POINTER(ctypes.c_int32)
+        L.gi_kat_x_query.argtypes = [vp, i32, dp, dp, i32, ip, dp, ip, ip, ip, dp, ip, dp]
+        L.gi_kat_x_variant.argtypes = [vp, i32, ip]
         L.gi_scene_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)]
         L.gi_scene_x_form.argtypes = [vp, ctypes.POINTER(Opts), ctypes.POINTER(ctypes.c_int32)]
         L.gi_scene_r_kernel.argtypes = [vp, ctypes.POINTER(Opts), ctypes.POINTER(ctypes.c_int32)]
@@ -521,6 +525,32 @@ class DeviceScene:
         _check(lib().gi_trace_ray(self._h, _d3(origin), _d3(direction), _d3(light), ctypes.byref(hit), rgb),
                "gi_trace_ray")
         return hit, tuple(rgb)
+
+    def kat_x_variant(self, flags: int = 0) -> dict:
+        """The kernel variant kat_x_query runs with these flags (flags 0: k_seg's for this scene):
+        {"LDS", "W4", "SH", "TRI", "CN", "FLAT"} -> bool (gi_kat_x_variant)."""
+        out = (ctypes.c_int32 * 6)()
+        _check(lib().gi_kat_x_variant(self._h, int(flags), out), "gi_kat_x_variant")
+        return dict(zip(("LDS", "W4", "SH", "TRI", "CN", "FLAT"), (bool(v) for v in out)))
+
+    def kat_x_query(self, recs: np.ndarray, cam_pos, flags: int = 0) -> dict:
+        """Ray-level Mode X queries on the device (gi_kat_x_query; a test hook): records (o, d, light,
+        d2) of 12 doubles -> prim1, t1, occl, skip_s, prim2, t2, skip2 per ray and the scalar skip_cos
+        (None for no rays).  flags: KAT_X_TREE walks the tree where the flat leaf table would apply,
+        KAT_X_HBM runs the HBM-resident variant on a scene staged in LDS."""
+        recs = np.ascontiguousarray(recs, np.float64).reshape(-1, 12)
+        n = recs.shape[0]
+        out = dict(prim1=np.zeros(n, np.int32), t1=np.zeros(n), occl=np.zeros(n, np.int32), skip_s=np.zeros(n, np.int32),
+                   prim2=np.zeros(n, np.int32), t2=np.zeros(n), skip2=np.zeros(n, np.int32))
+        sc = ctypes.c_double(float("nan"))
+        ip, dp = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)
+        _check(lib().gi_kat_x_query(self._h, n, recs.ctypes.data_as(dp), _d3(cam_pos), int(flags),
+                                    out["prim1"].ctypes.data_as(ip), out["t1"].ctypes.data_as(dp),
+                                    out["occl"].ctypes.data_as(ip), out["skip_s"].ctypes.data_as(ip),
+                                    out["prim2"].ctypes.data_as(ip), out["t2"].ctypes.data_as(dp),
+                                    out["skip2"].ctypes.data_as(ip), ctypes.byref(sc)), "gi_kat_x_query")
+        out["skip_cos"] = sc.value if n else None
+        return out
 
 
 def devices_from_env(default=None):

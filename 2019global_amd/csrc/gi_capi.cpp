@@ -37,6 +37,9 @@ hipError_t launch_unshard(int w, int h, int shard_count, const double* packed, c
                           uint8_t* rgb8, hipStream_t stream);
 hipError_t launch_trace_ray(const DevScene& sc, V3 o, V3 d, V3 light, int32_t* out_i, double* out_d, hipStream_t stream);
 hipError_t launch_box_kat(int n, const double* recs, int32_t* out, hipStream_t stream);
+hipError_t launch_x_query(const DevScene& sc, const XLaunchCfg& xc, V3 cam_pos, int flags, int n, const double* recs,
+                          int32_t* oi, double* od, hipStream_t stream);
+void x_query_variant(const DevScene& sc, const XLaunchCfg& xc, int flags, int32_t out[6]);
 }  // namespace gi
 
 using namespace gi;
@@ -544,6 +547,12 @@ int scene_create_on(const gi_scene_desc* desc, int device, gi_scene** out) {
                     d.root_lo[k] = std::min(d.root_lo[k], h.xwnodes[0].lo[k][c]);
                     d.root_hi[k] = std::max(d.root_hi[k], h.xwnodes[0].hi[k][c]);
                 }
+    d.x_far_r = INFINITY;
+    for (int k = 0; k < 3; ++k)
+        if (d.root_lo[k] <= d.root_hi[k]) {
+            const float m = 16.0f * std::max(std::fabs(d.root_lo[k]), std::fabs(d.root_hi[k]));
+            d.x_far_r = std::isinf(d.x_far_r) ? m : std::max(d.x_far_r, m);
+        }
     if ((e = x_launch_config(d, device, s->xcfg)) != hipSuccess) return hip_fail(e, "occupancy query");
     *out = s.release();
     return GI_OK;
@@ -832,6 +841,56 @@ int gi_kat_expbox(int n, const double* recs, int32_t* out) {
         (void)hipFree(d_r);
         (void)hipFree(d_o);
         return e == hipSuccess ? GI_OK : hip_fail(e, "gi_kat_expbox");
+    });
+}
+
+int gi_kat_x_query(gi_scene* s, int n, const double* recs, const double cam_pos[3], int flags, int32_t* prim1, double* t1,
+                   int32_t* occl, int32_t* skip_s, int32_t* prim2, double* t2, int32_t* skip2, double* skip_cos) {
+    return guard([&]() -> int {
+        DeviceRestore keep;   // the caller's current device, restored on return
+        if (!s || !cam_pos || n < 0 || (flags & ~3) != 0) return fail(GI_ERR_ARG, "bad arguments");
+        if (n > 0 && (!recs || !prim1 || !t1 || !occl || !skip_s || !prim2 || !t2 || !skip2)) return fail(GI_ERR_ARG, "null argument");
+        if (n == 0) return GI_OK;
+        std::lock_guard<std::mutex> lk(s->mu);
+        int rc = bind_device(s->device);
+        if (rc) return rc;
+        double *d_r = nullptr, *d_d = nullptr;
+        int32_t* d_i = nullptr;
+        std::vector<int32_t> hi((size_t)n * 5);
+        std::vector<double> hd((size_t)n * 2 + 1);
+        hipError_t e;
+        if ((e = hipMalloc((void**)&d_r, (size_t)n * 12 * sizeof(double))) == hipSuccess &&
+            (e = hipMalloc((void**)&d_i, hi.size() * sizeof(int32_t))) == hipSuccess)
+            e = hipMalloc((void**)&d_d, hd.size() * sizeof(double));
+        if (e == hipSuccess) e = hipMemcpy(d_r, recs, (size_t)n * 12 * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess)
+            e = launch_x_query(s->dev, s->xcfg, v3(cam_pos[0], cam_pos[1], cam_pos[2]), flags, n, d_r, d_i, d_d, nullptr);
+        if (e == hipSuccess) e = hipMemcpy(hi.data(), d_i, hi.size() * sizeof(int32_t), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(hd.data(), d_d, hd.size() * sizeof(double), hipMemcpyDeviceToHost);
+        (void)hipFree(d_r);
+        (void)hipFree(d_i);
+        (void)hipFree(d_d);
+        if (e != hipSuccess) return hip_fail(e, "gi_kat_x_query");
+        for (size_t i = 0; i < (size_t)n; ++i) {
+            prim1[i] = hi[5 * i];
+            occl[i] = hi[5 * i + 1];
+            skip_s[i] = hi[5 * i + 2];
+            prim2[i] = hi[5 * i + 3];
+            skip2[i] = hi[5 * i + 4];
+            t1[i] = hd[2 * i];
+            t2[i] = hd[2 * i + 1];
+        }
+        if (skip_cos) *skip_cos = hd[2 * (size_t)n];
+        return GI_OK;
+    });
+}
+
+int gi_kat_x_variant(gi_scene* s, int flags, int32_t out[6]) {
+    return guard([&]() -> int {
+        if (!s || !out || (flags & ~3) != 0) return fail(GI_ERR_ARG, "bad arguments");
+        std::lock_guard<std::mutex> lk(s->mu);
+        x_query_variant(s->dev, s->xcfg, flags, out);
+        return GI_OK;
     });
 }
 

@@ -189,6 +189,37 @@ __device__ __forceinline__ F3 inv_dir(V3 d) {
               __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf((float)d.y), -1e30f, 1e30f),
               __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf((float)d.z), -1e30f, 1e30f));
 }
+// The origin of a ray's fp32 box tests.  The slab arithmetic rounds three times at about 2^-24 |o|
+// (the cast of o, -(o * iv), the fma), which the boxes' padding of 1e-5 extents covers up to |o| of
+// about 50 extents.  A ray that starts more than far_r = 16 extents out (DevScene::x_far_r) is
+// therefore tested from a point of itself near the scene: t0 = its closest approach to the world
+// origin less 4 extents.  Every primitive and padded box lies within 2 extents of the world origin
+// and every point of the ray before t0 at least 4 away, so nothing lies before that point (the slab
+// tests clamp at its t = 0), and a ray that passes the scene reaches it within 4.5 extents of the
+// origin.  The box distances then count from that point while the best t counts from o: the bound
+// the boxes are culled against is larger by t0 >= 0, which only culls less.  The fp64 primitive
+// tests keep the ray as given, so every (t, primitive) is unchanged.
+__device__ __forceinline__ F3 ray_org32(V3 o, V3 d, float far_r) {
+    F3 of = f3((float)o.x, (float)o.y, (float)o.z);
+    if (far_r < INFINITY) {   // uniform over the launch (ray_far_r): a scalar branch, not taken for near cameras
+        if (fmax(fabs(o.x), fmax(fabs(o.y), fabs(o.z))) > (double)far_r) {
+            const double dd = dot(d, d);
+            const double t0 = -dot(o, d) / dd - 0.25 * (double)far_r / gsqrt(dd);
+            if (t0 > 0.0) {   // (false for NaN: a zero direction keeps o)
+                const V3 oc = o + t0 * d;
+                of = f3((float)oc.x, (float)oc.y, (float)oc.z);
+            }
+        }
+    }
+    return of;
+}
+// The far_r a launch's closest-hit queries pass: the scene's (DevScene::x_far_r) when the camera is that
+// far out, else INFINITY.  A path's rays start at the camera or at hit points, which lie inside the
+// scene's bounds, so only a far camera's launch has far origins; shadow rays start at hit points
+// and always pass INFINITY.
+__device__ __forceinline__ float ray_far_r(const DevScene& sc, V3 cam_pos) {
+    return fmax(fabs(cam_pos.x), fmax(fabs(cam_pos.y), fabs(cam_pos.z))) > (double)sc.x_far_r ? sc.x_far_r : INFINITY;
+}
 __device__ __forceinline__ F3 neg_oiv(F3 of, F3 ivf) { return f3(-(of.x * ivf.x), -(of.y * ivf.y), -(of.z * ivf.z)); }
 // Near / far planes: on axis a a box's entry plane is its min plane when iv_a >= 0 and its max
 // plane otherwise, for every box -- fma(b, iv, -o*iv) is monotone in the plane b, rounding included

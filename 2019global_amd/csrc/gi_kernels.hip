@@ -2553,6 +2553,36 @@ hipError_t launch_box_kat(int n, const double* recs, int32_t* out, hipStream_t s
     return hipGetLastError();
 }
 
+// gi_kat_x_query: the variant, the flat choice and the dynamic LDS of a k_seg launch on this scene
+// (launch_render's xc.kv, xc.wf_lds_bytes and bit 6).  flags bit 0: the tree walk where the flat
+// table would apply (GI_X_FLAT=0 in process); bit 1: the HBM-resident variants (kv = 0: the level
+// stack instead of the staged scene) for a scene that would be staged in LDS.
+hipError_t launch_x_query_kat(const DevScene& sc, int kv, bool flat, size_t lds_bytes, V3 cam_pos, int n,
+                              const double* recs, int32_t* oi, double* od, hipStream_t stream);
+void wf_variant(const DevScene& sc, int kv, bool flat, int32_t out[6]);
+namespace {
+struct XQueryCfg {
+    int kv;
+    size_t lds_bytes;
+    bool flat;
+};
+XQueryCfg x_query_cfg(const XLaunchCfg& xc, int flags) {
+    const bool hbm = (flags & 2) != 0 && xc.kv >= 2;
+    return XQueryCfg{hbm ? 0 : xc.kv, hbm ? 16 * 256 * sizeof(int) + wf_slot_bytes() : xc.wf_lds_bytes,
+                     x_env().flat && (flags & 1) == 0};
+}
+}  // namespace
+hipError_t launch_x_query(const DevScene& sc, const XLaunchCfg& xc, V3 cam_pos, int flags, int n, const double* recs,
+                          int32_t* oi, double* od, hipStream_t stream) {
+    const XQueryCfg c = x_query_cfg(xc, flags);
+    return launch_x_query_kat(sc, c.kv, c.flat, c.lds_bytes, cam_pos, n, recs, oi, od, stream);
+}
+// the kernel variant (LDS, W4, SH, TRI, CN, FLAT) that launch runs -- with flags 0, k_seg's for this scene
+void x_query_variant(const DevScene& sc, const XLaunchCfg& xc, int flags, int32_t out[6]) {
+    const XQueryCfg c = x_query_cfg(xc, flags);
+    wf_variant(sc, c.kv, c.flat, out);
+}
+
 hipError_t launch_trace_ray(const DevScene& sc, V3 o, V3 d, V3 light, int32_t* out_i, double* out_d, hipStream_t stream) {
     hipLaunchKernelGGL(k_trace_ray, dim3(1), dim3(64), 0, stream, sc, o, d, light, out_i, out_d);
     return hipGetLastError();

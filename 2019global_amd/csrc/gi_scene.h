@@ -246,6 +246,8 @@ struct DevScene {
     const XFlatLeaf* xflat;
     int32_t n_xflat;
     int32_t x_flat;        // 1: the scene is staged in LDS and its table fits (k_seg / k_wf_bounce use wf_flat)
+    float x_far_r;         // 16 x max |coordinate| of root_lo / root_hi (inf: no primitive): rays that start
+                           // farther out run their fp32 box tests from a point near the scene (gi_dev.h ray_org32)
 };
 
 // HIP events bracketing the dominant kernel of renders issued with GI_FLAG_TIME (owned by the

@@ -73,12 +73,12 @@ struct WFQ {
 // fetched one ahead of their test.  LDS-resident scenes (!NST), closest hit: a popped child is
 // re-tested against the current best t (its box is a ds_read away).
 template <bool ANY, bool PAIR, bool AXIS, bool SH, bool TRI, bool NST, typename NodeP, typename HotP>
-__device__ __forceinline__ int wf_trace(NodeP W, HotP H, V3 o, V3 d, double tmax, bool act, int* nst, double& t_out,
+__device__ __forceinline__ int wf_trace(float far_r, NodeP W, HotP H, V3 o, V3 d, double tmax, bool act, int* nst, double& t_out,
                                         uint32_t& nnode, uint32_t& nprim, uint32_t& nsteps, int skip = 254) {
     // the own-plane skip (XWNode scenes; gi_build.cpp assign_plane_groups): leaves of group skip are
     // never entered -- their exact tests would all find t below MX_TMIN for this ray
     constexpr bool kSkip = std::is_same<NodeP, const XWNode*>::value;
-    const F3 of = f3((float)o.x, (float)o.y, (float)o.z);
+    const F3 of = ray_org32(o, d, far_r);
     const F3 ivf = inv_dir(d);
     const int dmask = (d.x < 0 ? 1 : 0) | (d.y < 0 ? 2 : 0) | (d.z < 0 ? 4 : 0);
     double tb = tmax;
@@ -241,9 +241,9 @@ __device__ __forceinline__ bool flat_hit(const XFlatLeaf* r, F3 no, F3 ivf, int 
     return tn <= tf;
 }
 template <bool ANY, bool TRI>
-__device__ __forceinline__ int wf_flat(const XFlatLeaf* tab, int n, const XHot* H, V3 o, V3 d, double tmax, bool act,
+__device__ __forceinline__ int wf_flat(float far_r, const XFlatLeaf* tab, int n, const XHot* H, V3 o, V3 d, double tmax, bool act,
                                        double& t_out, uint32_t& nnode, uint32_t& nprim, uint32_t& nsteps, int skip) {
-    const F3 of = f3((float)o.x, (float)o.y, (float)o.z);
+    const F3 of = ray_org32(o, d, far_r);
     const F3 ivf = inv_dir(d);
     const F3 no = neg_oiv(of, ivf);
     const int sm = iv_signs(ivf);
@@ -430,7 +430,7 @@ __device__ __forceinline__ V3 wf_primary(const CamDev& cam, const TileMap& m, un
 // exactly +0 (the oracle traces it and adds L = 0)
 __device__ __forceinline__ bool wf_primary_misses(const DevScene& sc, const CamDev& cam, V3 d0) {
     const F3 iv0 = f3(__builtin_amdgcn_rcpf((float)d0.x), __builtin_amdgcn_rcpf((float)d0.y), __builtin_amdgcn_rcpf((float)d0.z));
-    return !root_hit(sc, f3((float)cam.pos.x, (float)cam.pos.y, (float)cam.pos.z), iv0);
+    return !root_hit(sc, ray_org32(cam.pos, d0, ray_far_r(sc, cam.pos)), iv0);   // (a far camera: tested from near the scene)
 }
 // the path's radiance once it ends: its per-sample row (spp > 1; k_x_reduce adds a pixel's rows in
 // sample order) or, with one sample, the pixel: min((0 + L) / 1, 1), the reduce pass's operations
@@ -469,7 +469,7 @@ template <bool STATS, bool LDS, bool SH, bool TRI, bool CN, bool FLAT, typename 
 __device__ __forceinline__ bool x_segment(const DevScene& sc, const WFView& v, const V3& light, int depth, bool no_shadow, bool act,
                                           const KeyF& id_of, V3& o, V3& d, V3& L, V3& T,
                                           uint32_t& nnode, uint32_t& nprim, uint32_t& nrays, WFSegStats& ws,
-                                          double skip_cos = 2.0, int* splane = nullptr) {
+                                          double skip_cos = 2.0, int* splane = nullptr, float far_r = INFINITY) {
     uint32_t st_steps = 0;
     uint64_t c0 = STATS ? clock64() : 0;
     V3 P = o, Ld = v3(0, 0, 1);
@@ -479,10 +479,10 @@ __device__ __forceinline__ bool x_segment(const DevScene& sc, const WFView& v, c
     int best;
     // the own-plane skip of this ray (k_seg carries it from the previous segment; 254: none)
     const int skip_c = splane ? *splane : 254;
-    if constexpr (FLAT) best = wf_flat<false, TRI>(v.FT, sc.n_xflat, v.LH, o, d, INFINITY, act, tbest, nnode, nprim, st_steps, skip_c);
-    else if constexpr (LDS) best = wf_trace<false, true, false, SH, TRI, false>(v.LW, v.LH, o, d, INFINITY, act, v.nst, tbest, nnode, nprim, st_steps, skip_c);
-    else if constexpr (CN) best = wf_trace<false, false, false, SH, TRI, true>(sc.xcnodes, sc.xhot, o, d, INFINITY, act, v.nst, tbest, nnode, nprim, st_steps);
-    else best = wf_trace<false, false, false, SH, TRI, true>(sc.xwnodes, sc.xhot, o, d, INFINITY, act, v.nst, tbest, nnode, nprim, st_steps, skip_c);
+    if constexpr (FLAT) best = wf_flat<false, TRI>(far_r, v.FT, sc.n_xflat, v.LH, o, d, INFINITY, act, tbest, nnode, nprim, st_steps, skip_c);
+    else if constexpr (LDS) best = wf_trace<false, true, false, SH, TRI, false>(far_r, v.LW, v.LH, o, d, INFINITY, act, v.nst, tbest, nnode, nprim, st_steps, skip_c);
+    else if constexpr (CN) best = wf_trace<false, false, false, SH, TRI, true>(far_r, sc.xcnodes, sc.xhot, o, d, INFINITY, act, v.nst, tbest, nnode, nprim, st_steps);
+    else best = wf_trace<false, false, false, SH, TRI, true>(far_r, sc.xwnodes, sc.xhot, o, d, INFINITY, act, v.nst, tbest, nnode, nprim, st_steps, skip_c);
     if (act) ++nrays;
     if (STATS) {
         wf_wave_steps(st_steps, ws.it_c, ws.ln_c);
@@ -509,10 +509,10 @@ __device__ __forceinline__ bool x_segment(const DevScene& sc, const WFView& v, c
         double tdummy;
         int sb;
         const int skip_s = (pg < 254 && fabs(dot(Ld, pn)) >= skip_cos) ? pg : 254;
-        if constexpr (FLAT) sb = wf_flat<true, TRI>(v.FT, sc.n_xflat, v.LH, P, Ld, ldist, hit, tdummy, nnode, nprim, st_steps, skip_s);
-        else if constexpr (LDS) sb = wf_trace<true, true, false, SH, TRI, false>(v.LW, v.LH, P, Ld, ldist, hit, v.nst, tdummy, nnode, nprim, st_steps, skip_s);
-        else if constexpr (CN) sb = wf_trace<true, false, false, SH, TRI, true>(sc.xcnodes, sc.xhot, P, Ld, ldist, hit, v.nst, tdummy, nnode, nprim, st_steps);
-        else sb = wf_trace<true, false, false, SH, TRI, true>(sc.xwnodes, sc.xhot, P, Ld, ldist, hit, v.nst, tdummy, nnode, nprim, st_steps, skip_s);
+        if constexpr (FLAT) sb = wf_flat<true, TRI>(INFINITY, v.FT, sc.n_xflat, v.LH, P, Ld, ldist, hit, tdummy, nnode, nprim, st_steps, skip_s);
+        else if constexpr (LDS) sb = wf_trace<true, true, false, SH, TRI, false>(INFINITY, v.LW, v.LH, P, Ld, ldist, hit, v.nst, tdummy, nnode, nprim, st_steps, skip_s);
+        else if constexpr (CN) sb = wf_trace<true, false, false, SH, TRI, true>(INFINITY, sc.xcnodes, sc.xhot, P, Ld, ldist, hit, v.nst, tdummy, nnode, nprim, st_steps);
+        else sb = wf_trace<true, false, false, SH, TRI, true>(INFINITY, sc.xwnodes, sc.xhot, P, Ld, ldist, hit, v.nst, tdummy, nnode, nprim, st_steps, skip_s);
         occl = sb >= 0;
         if (STATS) wf_wave_steps(st_steps, ws.it_s, ws.ln_s);
     }
@@ -659,9 +659,10 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
         WFSegStats ws;
         // (the queue carries no plane: the closest ray is not skipped here, the shadow ray is)
         const double skip_cos = sc.x_skip_a * fmax(fabs(cam.pos.x), fmax(fabs(cam.pos.y), fabs(cam.pos.z))) + sc.x_skip_b;
+        const float far_r = ray_far_r(sc, cam.pos);   // (far cameras: gi_dev.h ray_org32)
         int splane = 254;
         const bool cont = x_segment<false, LDS, SH, TRI, CN, FLAT>(sc, v, light, depth, no_shadow, act, [&] { return PathId{key, smp, b}; }, o, d, L, T,
-                                                             nnode, nprim, nrays, ws, skip_cos, &splane);
+                                                             nnode, nprim, nrays, ws, skip_cos, &splane, far_r);
         // ---- live paths to the next bounce's queue: one atomic per wave, entries in lane order
         const unsigned long long mc = __ballot(cont);
         if (mc) {
@@ -735,6 +736,7 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
     int splane = 254;   // the own-plane skip of the lane's next ray (254: none; primary rays)
     // (gi_build.cpp assign_plane_groups: the bound on |d . n| above which a surface's own plane is skipped)
     const double skip_cos = sc.x_skip_a * fmax(fabs(cam.pos.x), fmax(fabs(cam.pos.y), fabs(cam.pos.z))) + sc.x_skip_b;
+    const float far_r = ray_far_r(sc, cam.pos);   // (far cameras: gi_dev.h ray_org32)
     WFSegStats ws;
     const uint64_t t_begin = STATS ? clock64() : 0;
     for (;;) {
@@ -818,7 +820,7 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
         const bool cont = x_segment<STATS, LDS, SH, TRI, CN, FLAT>(
             sc, v, light, depth, no_shadow, live,
             [&] { return PathId{slot_get_u64(v.pl, 6), (unsigned)(slot_get_u64(v.pl, 7) >> 32), (int)slot_get_u64(v.pl, 8)}; },
-            o, d, L, T, nnode, nprim, nrays, ws, skip_cos, &splane);
+            o, d, L, T, nnode, nprim, nrays, ws, skip_cos, &splane, far_r);
         if (live) {
             if (cont) {
                 slot_put_u64(v.pl, 8, slot_get_u64(v.pl, 8) + 1);
@@ -849,6 +851,81 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
         for (int off = 32; off > 0; off >>= 1) r += __shfl_xor(r, off);
         if (lane == 0 && r) atomicAdd(stats + GI_STAT_X_RESOLVED, (unsigned long long)r);
     }
+}
+
+// Known-answer hook (gi_kat_x_query; tests): the three queries of one path segment, one ray per
+// lane, with x_segment's calls and template arguments and k_seg's staging, so a test sees the
+// (t, primitive) answers themselves.  Record i: o, d, light, d2 (12 doubles).  The closest hit of
+// (o, d) without a skip; from its point P the any-hit query toward the light and the closest hit
+// of (P, d2), each with the own-plane skip by x_segment's rule.  Lanes past n run the queries
+// without a ray.  oi[5 i ..]: prim1, occl (-1 without a hit), skip_s, prim2, skip2; od[2 i ..]:
+// t1, t2; od[2 n]: the launch's skip_cos.
+template <bool LDS, bool W4, bool SH, bool TRI, bool CN, bool FLAT>
+__global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_WAVES) void k_x_query_kat(
+    DevScene sc, V3 cam_pos, int n, const double* recs, int32_t* oi, double* od) {
+    extern __shared__ int4 lds_dyn[];
+    const WFView v = wf_stage<LDS>(sc, lds_dyn);
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bool act = i < (long long)n;
+    // (k_seg's expression)
+    const double skip_cos = sc.x_skip_a * fmax(fabs(cam_pos.x), fmax(fabs(cam_pos.y), fabs(cam_pos.z))) + sc.x_skip_b;
+    const float far_r = ray_far_r(sc, cam_pos);   // (as k_seg: gi_dev.h ray_org32)
+    V3 o = v3(0, 0, 0), d = v3(1, 0, 0), light = v3(0, 0, 0), d2 = v3(1, 0, 0);
+    if (act) {
+        const double* q = recs + 12 * i;
+        o = v3(q[0], q[1], q[2]);
+        d = v3(q[3], q[4], q[5]);
+        light = v3(q[6], q[7], q[8]);
+        d2 = v3(q[9], q[10], q[11]);
+    }
+    uint32_t nnode = 0, nprim = 0, st_steps = 0;
+    // ---- closest hit (x_segment's calls, a primary ray: no skip)
+    double t1 = INFINITY;
+    int p1;
+    if constexpr (FLAT) p1 = wf_flat<false, TRI>(far_r, v.FT, sc.n_xflat, v.LH, o, d, INFINITY, act, t1, nnode, nprim, st_steps, 254);
+    else if constexpr (LDS) p1 = wf_trace<false, true, false, SH, TRI, false>(far_r, v.LW, v.LH, o, d, INFINITY, act, v.nst, t1, nnode, nprim, st_steps, 254);
+    else if constexpr (CN) p1 = wf_trace<false, false, false, SH, TRI, true>(far_r, sc.xcnodes, sc.xhot, o, d, INFINITY, act, v.nst, t1, nnode, nprim, st_steps);
+    else p1 = wf_trace<false, false, false, SH, TRI, true>(far_r, sc.xwnodes, sc.xhot, o, d, INFINITY, act, v.nst, t1, nnode, nprim, st_steps, 254);
+    const bool hit = act && p1 >= 0;
+    V3 P = o, Ld = v3(0, 0, 1);
+    double ldist = 0.0;
+    int pg = 254;
+    V3 pn = v3(0, 0, 1);
+    if (hit) {
+        P = o + t1 * d;
+        const V3 lv = light - P;
+        ldist = gsqrt(dot(lv, lv));
+        Ld = normalize(lv);
+        const XPrim& px = v.XP[p1];
+        pg = px.pad[0] < 254 ? px.pad[0] : 254;
+        pn = ld3(px.n);
+    }
+    // ---- shadow any-hit
+    double tdummy;
+    int sb;
+    const int skip_s = (pg < 254 && fabs(dot(Ld, pn)) >= skip_cos) ? pg : 254;
+    if constexpr (FLAT) sb = wf_flat<true, TRI>(INFINITY, v.FT, sc.n_xflat, v.LH, P, Ld, ldist, hit, tdummy, nnode, nprim, st_steps, skip_s);
+    else if constexpr (LDS) sb = wf_trace<true, true, false, SH, TRI, false>(INFINITY, v.LW, v.LH, P, Ld, ldist, hit, v.nst, tdummy, nnode, nprim, st_steps, skip_s);
+    else if constexpr (CN) sb = wf_trace<true, false, false, SH, TRI, true>(INFINITY, sc.xcnodes, sc.xhot, P, Ld, ldist, hit, v.nst, tdummy, nnode, nprim, st_steps);
+    else sb = wf_trace<true, false, false, SH, TRI, true>(INFINITY, sc.xwnodes, sc.xhot, P, Ld, ldist, hit, v.nst, tdummy, nnode, nprim, st_steps, skip_s);
+    // ---- the next segment's closest hit, leaving the surface along d2
+    const int skip2 = (pg < 254 && fabs(dot(d2, pn)) >= skip_cos) ? pg : 254;
+    double t2 = INFINITY;
+    int p2;
+    if constexpr (FLAT) p2 = wf_flat<false, TRI>(far_r, v.FT, sc.n_xflat, v.LH, P, d2, INFINITY, hit, t2, nnode, nprim, st_steps, skip2);
+    else if constexpr (LDS) p2 = wf_trace<false, true, false, SH, TRI, false>(far_r, v.LW, v.LH, P, d2, INFINITY, hit, v.nst, t2, nnode, nprim, st_steps, skip2);
+    else if constexpr (CN) p2 = wf_trace<false, false, false, SH, TRI, true>(far_r, sc.xcnodes, sc.xhot, P, d2, INFINITY, hit, v.nst, t2, nnode, nprim, st_steps);
+    else p2 = wf_trace<false, false, false, SH, TRI, true>(far_r, sc.xwnodes, sc.xhot, P, d2, INFINITY, hit, v.nst, t2, nnode, nprim, st_steps, skip2);
+    if (act) {
+        oi[5 * i] = p1 >= 0 ? p1 : -1;
+        oi[5 * i + 1] = hit ? (sb >= 0 ? 1 : 0) : -1;
+        oi[5 * i + 2] = skip_s;
+        oi[5 * i + 3] = (hit && p2 >= 0) ? p2 : -1;
+        oi[5 * i + 4] = skip2;
+        od[2 * i] = p1 >= 0 ? t1 : INFINITY;
+        od[2 * i + 1] = (hit && p2 >= 0) ? t2 : INFINITY;
+    }
+    if (i == 0) od[2 * (long long)n] = skip_cos;
 }
 
 }  // namespace
@@ -964,6 +1041,27 @@ hipError_t launch_wf(const DevScene& sc, int kv, size_t lds_bytes, int resident,
     }
     if (ev_end) (void)hipEventRecord(ev_end, stream);
     return hipGetLastError();
+}
+
+// gi_kat_x_query's launch: k_seg's variant for the scene (wf_dispatch), one ray per lane
+hipError_t launch_x_query_kat(const DevScene& sc, int kv, bool flat, size_t lds_bytes, V3 cam_pos, int n,
+                              const double* recs, int32_t* oi, double* od, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    const dim3 grid((unsigned)(((long long)n + 255) / 256)), block(256);
+    wf_dispatch(sc, kv, flat, [&](auto L, auto W, auto SHt, auto T, auto C, auto FL) {
+        constexpr bool l = decltype(L)::value, wv = decltype(W)::value, sh = decltype(SHt)::value,
+                       t = decltype(T)::value, c = decltype(C)::value, fl = decltype(FL)::value;
+        hipLaunchKernelGGL((k_x_query_kat<l, wv, sh, t, c, fl>), grid, block, lds_bytes, stream, sc, cam_pos, n, recs, oi, od);
+    });
+    return hipGetLastError();
+}
+
+// the variant (LDS, W4, SH, TRI, CN, FLAT) wf_dispatch picks for a scene: what gi_kat_x_variant reports
+void wf_variant(const DevScene& sc, int kv, bool flat, int32_t out[6]) {
+    wf_dispatch(sc, kv, flat, [&](auto L, auto W, auto SHt, auto T, auto C, auto FL) {
+        out[0] = decltype(L)::value; out[1] = decltype(W)::value; out[2] = decltype(SHt)::value;
+        out[3] = decltype(T)::value; out[4] = decltype(C)::value; out[5] = decltype(FL)::value;
+    });
 }
 
 }  // namespace gi

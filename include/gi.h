@@ -18,6 +18,8 @@
  *   gi_unshard_device    reassembles a frame from per-rank packed tiles after the RCCL gather
  *   gi_scene_kernel_ms   HIP-event duration of the last timed render's dominant kernel (bench)
  *   gi_scene_x_form      which Mode X form (persistent kernel / wavefront) a render would run
+ *   gi_kat_*             known-answer TEST hooks: the device's ExpBox node test and the Mode X
+ *                        queries ray by ray (gi_kat_x_query, gi_kat_x_variant)
  *   gi_octree_*          Octree(min,max) + push_back (octree.h:14-43) and the public query
  *                        Octree::intersect(const Ray&) (octree.h:46-68 -> Node::intersect :132-155)
  *                        on the host, for reference-side callers of the candidate list
@@ -43,7 +45,7 @@
 extern "C" {
 #endif
 
-#define GI_ABI_VERSION 10
+#define GI_ABI_VERSION 11
 
 typedef enum gi_status {
     GI_OK = 0,
@@ -322,6 +324,27 @@ int gi_obj_parse(const char* text, int64_t len, const gi_entity_desc* tmpl, gi_e
 /* Known-answer hook: the device's ExpBox node test (entities.h:379-440 as octree.h:141-146 uses
  * it) over n host records (min[3], max[3], origin[3], dir[3]); out[i] = 0/1. */
 int gi_kat_expbox(int n, const double* recs, int32_t* out);
+
+/* Known-answer hook (a TEST hook; ABI 11): the Mode X device queries ray by ray.  n host records of
+ * 12 doubles -- o[3], d[3], light[3], d2[3]; d and d2 are used as given -- each run as one path
+ * segment's three queries by the kernel variant the segment form (k_seg) runs for this scene, the
+ * scene staged as k_seg stages it:
+ *   prim1, t1 : the closest hit of the ray (o, d): primitive index (entities in push order, an
+ *               ExpQuad as its 2 triangles) and distance; -1 and +inf without a hit;
+ *   occl      : from the hit point P = o + t1 d, 1 / 0 whether anything lies between P and `light`
+ *               (-1 without a hit); skip_s: the plane group this shadow ray skipped (254: none);
+ *   prim2, t2 : the closest hit of the ray (P, d2); skip2: the plane group it skipped.
+ * *skip_cos (may be NULL): the own-plane skip's bound on |d . n| for a camera at cam_pos.
+ * flags: bit 0 walks the tree where the scene's flat leaf table would apply (as GI_X_FLAT=0); bit 1
+ * runs the HBM-resident variant on a scene that is staged in LDS.  n = 0 launches nothing. */
+int gi_kat_x_query(gi_scene* scene, int n, const double* recs, const double cam_pos[3], int flags, int32_t* prim1,
+                   double* t1, int32_t* occl, int32_t* skip_s, int32_t* prim2, double* t2, int32_t* skip2,
+                   double* skip_cos);
+/* The kernel variant gi_kat_x_query runs for these flags -- with flags 0 the segment form's own for
+ * this scene: out[0..5] = 1/0 for LDS (scene staged in LDS), W4 (4 waves per SIMD), SH (level masks
+ * in one word: trees of at most 8 levels), TRI (triangles only), CN (quantised nodes), FLAT (the flat
+ * leaf table answers the queries). */
+int gi_kat_x_variant(gi_scene* scene, int flags, int32_t out[6]);
 
 #ifdef __cplusplus
 }

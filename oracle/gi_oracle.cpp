@@ -1442,4 +1442,51 @@ int gio_boxes(int n, const double* recs, int32_t* out) {
     return 0;
 }
 
+// Ray-level Mode X queries (the known-answer reference of the device hook gi_kat_x_query): per
+// record the three queries of one path segment of sample_mode_x, with the same operations --
+// closest hit of (o, d); from its point P the shadow query toward `light`; the closest hit of
+// (P, d2).  d and d2 are used as given.  nties: primitives whose t equals the best t (brute force).
+int gio_x_query(const char* scn, int n, const double* recs, int32_t* prim1, double* t1, int32_t* occl, int32_t* prim2,
+                double* t2, int32_t* nties1, int32_t* nties2) {
+    Scene s;
+    if (!parse(scn, s, false)) return -1;
+    if (n < 0 || (n > 0 && !recs)) { g_err = "bad arguments"; return -2; }
+    std::vector<Prim> prims;
+    OAccel A;
+    build_prims(s, prims);
+    build_accel(prims, A);
+    auto ties = [&](V3 o, V3 d, double tb) {
+        int c = 0;
+        for (const Prim& p : prims)
+            if (mx_prim_t(p, o, d, MX_TMIN) == tb) ++c;
+        return c;
+    };
+#pragma omp parallel for schedule(dynamic, 64)
+    for (int i = 0; i < n; ++i) {
+        const double* q = recs + 12 * (size_t)i;
+        const V3 o{q[0], q[1], q[2]}, d{q[3], q[4], q[5]}, light{q[6], q[7], q[8]}, d2{q[9], q[10], q[11]};
+        double ta = INFINITY, tb = INFINITY;
+        const int pa = mx_closest(prims, A, o, d, ta);
+        int pb = -1, oc = -1, na = 0, nb = 0;
+        if (pa >= 0) {
+            const V3 P = o + ta * d;
+            const V3 lv = light - P;
+            const double ldist = std::sqrt(dot(lv, lv));
+            const V3 Ld = normalize(lv);
+            oc = mx_occluded(prims, A, P, Ld, ldist) ? 1 : 0;
+            pb = mx_closest(prims, A, P, d2, tb);
+            if (nties1) na = ties(o, d, ta);
+            if (nties2 && pb >= 0) nb = ties(P, d2, tb);
+        }
+        if (prim1) prim1[i] = pa;
+        if (t1) t1[i] = ta;
+        if (occl) occl[i] = oc;
+        if (prim2) prim2[i] = pb;
+        if (t2) t2[i] = tb;
+        if (nties1) nties1[i] = na;
+        if (nties2) nties2[i] = nb;
+    }
+    return 0;
+}
+
 }  // extern "C"

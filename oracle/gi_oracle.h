@@ -51,6 +51,15 @@ int gio_boxes(int n, const double* recs, int32_t* out);
 void gio_set_accel(int mode);
 void gio_set_no_shadow(int on);   /* Mode X without shadow rays (GI_FLAG_X_NO_SHADOW; tests) */
 
+// Ray-level Mode X queries, n records of 12 doubles (o[3], d[3], light[3], d2[3]; d and d2 used as
+// given): the operations of one path segment of the Mode X integrator with its own closest-hit and
+// shadow queries (gio_set_accel applies).  prim1, t1: the closest hit of (o, d) (-1 and +inf: none).
+// With a hit at P = o + t1 d: occl = 1/0, the shadow query from P toward `light` (-1 without a
+// hit), and prim2, t2: the closest hit of (P, d2).  nties1 / nties2: the number of primitives whose t
+// equals t1 / t2 (counted by brute force; 0 without a hit).  Any output pointer may be NULL.
+int gio_x_query(const char* scn, int n, const double* recs, int32_t* prim1, double* t1, int32_t* occl, int32_t* prim2,
+                double* t2, int32_t* nties1, int32_t* nties2);
+
 const char* gio_last_error(void);
 
 #ifdef __cplusplus

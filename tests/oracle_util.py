@@ -55,6 +55,7 @@ def oracle():
         lib.gio_time_rows.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, f64p,
                                       f64p, ctypes.POINTER(ctypes.c_uint8)]
+        lib.gio_x_query.argtypes = [ctypes.c_char_p, ctypes.c_int, f64p, i32p, f64p, i32p, i32p, f64p, i32p, i32p]
         _oracle = lib
     return _oracle
 
@@ -108,6 +109,23 @@ def oracle_no_shadow(on: bool) -> None:
 def oracle_accel(mode: int) -> None:
     """Mode X queries: -1 default (BVH above 256 primitives), 0 brute force, 1 BVH."""
     oracle().gio_set_accel(mode)
+
+
+def oracle_x_query(scn: str, recs: np.ndarray) -> dict:
+    """Ray-level Mode X queries (gio_x_query) over records (o, d, light, d2) of 12 doubles: prim1, t1,
+    occl, prim2, t2 and the tie counts nties1, nties2.  oracle_accel() chooses brute force or the BVH."""
+    recs = np.ascontiguousarray(recs, np.float64).reshape(-1, 12)
+    n = recs.shape[0]
+    out = dict(prim1=np.zeros(n, np.int32), t1=np.zeros(n), occl=np.zeros(n, np.int32), prim2=np.zeros(n, np.int32),
+               t2=np.zeros(n), nties1=np.zeros(n, np.int32), nties2=np.zeros(n, np.int32))
+    lib = oracle()
+    rc = lib.gio_x_query(scn.encode(), n, _p(recs, ctypes.c_double), _p(out["prim1"], ctypes.c_int32),
+                         _p(out["t1"], ctypes.c_double), _p(out["occl"], ctypes.c_int32),
+                         _p(out["prim2"], ctypes.c_int32), _p(out["t2"], ctypes.c_double),
+                         _p(out["nties1"], ctypes.c_int32), _p(out["nties2"], ctypes.c_int32))
+    if rc != 0:
+        raise RuntimeError(f"gio_x_query failed ({rc}): {lib.gio_last_error().decode()}")
+    return out
 
 
 def oracle_tree(scn: str) -> str:

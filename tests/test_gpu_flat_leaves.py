@@ -3,7 +3,6 @@ GI_XFLAT_MAX leaves answer k_seg's closest-hit and shadow queries from the leaf 
 walking the tree.  Frames must not change: against the tree walk (GI_X_FLAT=0, a child process) and
 against the oracle at the edges of eligibility."""
 import os
-import re
 import subprocess
 import sys
 
@@ -11,14 +10,14 @@ import numpy as np
 import pytest
 
 import oracle_util as U
-from test_gpu_parity import _grazing_scene
+from x_scenes import (XFLAT_MAX, coincident_quads, empty as _empty, grazing_scene as _grazing_scene,
+                      one_triangle as _one_triangle, soup as _soup, three_record_leaves as _three_record_leaves,
+                      with_env as _with_env, with_sphere as _with_sphere)
 
 pytestmark = pytest.mark.gpu
 
 gi = U.pkg()
 S = U.scenes()
-XFLAT_MAX = int(re.search(r"#define GI_XFLAT_MAX (\d+)",
-                          open(os.path.join(U.ROOT, "2019global_amd", "csrc", "gi_scene.h")).read()).group(1))
 
 
 @pytest.fixture(scope="module")
@@ -87,68 +86,6 @@ def _render_stats(torch, d, sc, w, h, spp, depth, seed):
     return buf.cpu().numpy().reshape(-1, 3), st.cpu().numpy()
 
 
-def _with_env(env, make):
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return make()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _tri_scene(tris, name):
-    s = S.Scene()
-    s.name = name
-    for t, col in tris:
-        s.imp_triangle(*t, col)
-    return s
-
-
-def _one_triangle():
-    return _tri_scene([(((2.0, -3.0, -3.0), (2.0, 4.0, -2.0), (3.0, 0.0, 4.0)), (0.9, 0.6, 0.2))], "one_triangle"), {}
-
-
-def _empty():
-    s = S.Scene()
-    s.name = "empty"
-    return s, {}
-
-
-def _soup(n):
-    # single-primitive leaves (GI_XLEAF_MAX=1, read when the scene is built): n triangles, n leaves --
-    # rows of eight small tilted triangles in front of the camera
-    tris = []
-    for i in range(n):
-        x, y, z = 3.0 + 0.1 * (i % 3), -3.5 + (i % 8), -2.0 + (i // 8)
-        tris.append((((x, y - 0.4, z - 0.4), (x, y + 0.4, z - 0.4), (x + 0.2, y, z + 0.4)),
-                     (0.2 + 0.1 * (i % 8), 0.9 - 0.1 * (i % 7), 0.5)))
-    return _tri_scene(tris, "soup%d" % n), {"GI_XLEAF_MAX": "1"}
-
-
-def _three_record_leaves():
-    # four stacks of three parallel triangles: a stack's boxes coincide, so the builder keeps each as one
-    # leaf of three records (the pair loop's odd tail)
-    tris = []
-    # (close to the view axis: a 32 x 32 frame sees about +-0.4 around it at this distance)
-    for i, (y, z) in enumerate(((-0.3, -0.3), (0.3, -0.3), (-0.3, 0.3), (0.3, 0.3))):
-        for j in range(3):
-            x = 3.0 + 2.0 * i + 0.01 * j
-            tris.append((((x, y - 0.3, z - 0.3), (x, y + 0.3, z - 0.3), (x, y, z + 0.3)),
-                         (0.3 + 0.3 * j, 0.9 - 0.3 * j, 0.5)))
-    return _tri_scene(tris, "stacks"), {}
-
-
-def _with_sphere():
-    s = S.cornell_scene()
-    s.name = "cornell_sphere"
-    s.imp_sphere((4.0, 0.5, -1.0), 1.2, (0.8, 0.8, 0.3))
-    return s, {}
-
-
 EDGE = {"one_triangle": (_one_triangle, 1), "empty": (_empty, 0),
         "soup_max": (lambda: _soup(XFLAT_MAX), XFLAT_MAX), "soup_max_plus_1": (lambda: _soup(XFLAT_MAX + 1), None),
         "three_record_leaves": (_three_record_leaves, 4), "sphere": (_with_sphere, 18)}
@@ -186,12 +123,7 @@ def test_flat_query_edges_bit_exact_to_oracle(torch_cuda, case):
 def test_flat_query_equal_t_tie_break(torch_cuda):
     """Two coincident quads (every triangle duplicated, in another colour): each hit has two primitives
     at the same t, and the frame equals the oracle's, which keeps the smaller primitive index."""
-    q = [(3.0, -3.0, -3.0), (3.0, 3.0, -3.0), (3.5, 3.0, 3.0), (3.5, -3.0, 3.0)]
-    tris = []
-    for col in ((0.9, 0.2, 0.2), (0.2, 0.9, 0.2)):
-        tris.append(((q[0], q[1], q[2]), col))
-        tris.append(((q[0], q[2], q[3]), col))
-    sc = _tri_scene(tris, "coincident")
+    sc, _ = coincident_quads()
     d = gi.DeviceScene.from_scene(sc)
     w, h, spp, depth, seed = 24, 24, 2, 3, 7
     assert d.x_form(spp=spp, depth=depth) == "k_seg"

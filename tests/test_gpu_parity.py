@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import oracle_util as U
+from x_scenes import grazing_scene as _grazing_scene   # (shared with the flat-leaf and query tests)
 
 pytestmark = pytest.mark.gpu
 
@@ -1079,32 +1080,6 @@ def test_mode_r_reach_lane_groups_bit_exact(torch_cuda, tmp_path, group):
     ds = gi.DeviceScene.from_scene(st)
     rs, _ = ds.render(cam_of(st), st.light, 2048, 1088)
     assert U.bits_equal(rs, ref["strip"]).all(), "strip"
-
-
-def _grazing_scene(light_mode: str):
-    """The Cornell box plus two tilted quads (coplanar pairs on oblique planes), with the light put
-    almost into a surface's plane: "floor" 1e-9 above the floor (z = -5), "tilted" 1e-9 off the first
-    tilted quad's plane.  Shadow rays from that surface then leave it at an incidence ~1e-10, far
-    below the own-plane skip's bound, and must be traced unskipped."""
-    s = S.cornell_scene()
-    s.name = "grazing_" + light_mode
-    rng = np.random.default_rng(11)
-    centres = [np.array([4.0, 1.5, 0.5]), np.array([3.0, -2.0, 2.5])]
-    planes = []
-    for c in centres:
-        u = rng.normal(size=3); u /= np.linalg.norm(u)
-        v = np.cross(u, rng.normal(size=3)); v /= np.linalg.norm(v)
-        q = [c - u - v, c + u - v, c + u + v, c - u + v]
-        s.imp_triangle(tuple(q[0]), tuple(q[1]), tuple(q[2]), (1, 1, 1))
-        s.imp_triangle(tuple(q[0]), tuple(q[2]), tuple(q[3]), (1, 1, 1))
-        planes.append((c, np.cross(u, v)))
-    if light_mode == "floor":
-        s.light = (5.0, 0.5, -5.0 + 1e-9)
-    else:
-        c, n = planes[0]
-        w = np.cross(n, [0.0, 0.0, 1.0]); w /= np.linalg.norm(w)
-        s.light = tuple(c + 1.7 * w + 1e-9 * n)
-    return s
 
 
 @pytest.mark.parametrize("light_mode", ["floor", "tilted"])
