@@ -612,7 +612,7 @@ void build_xbvh(const std::vector<XPrim>& prims, const std::vector<double>& boun
     hs.x_handle8 = long_traversal ? 4 : 8;
     // short traversals also continue a path from its finished shadow ray inside the traversal
     // branch (measured +14% on the Cornell box, -5% on the 100k soup)
-    hs.x_flags = long_traversal ? 0 : 1;
+    hs.x_flags = long_traversal ? 0 : XF_INLINE_SHADOW;
 }
 
 // Mode R candidate reconstruction.  The reference's pixel is the LAST candidate of

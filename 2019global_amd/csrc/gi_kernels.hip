@@ -1302,7 +1302,7 @@ struct XWork {
 #define GI_X_MAX_RUN 1
 #endif
 
-// Shadow-ray handoff (HELP, xflags bit 3).  Once a wave has lanes with no work left (PH_DEAD: the
+// Shadow-ray handoff (HELP, XF_HANDOFF).  Once a wave has lanes with no work left (PH_DEAD: the
 // end of the frame, or of a small shard), a lane that has shaded a hit whose path continues gives
 // that hit's shadow ray to an idle lane and starts its next bounce ray at once, instead of tracing
 // the two one after the other: the path's critical path becomes max(shadow_b, closest_{b+1}) per
@@ -1334,39 +1334,39 @@ __device__ __forceinline__ void mode_x_wave(const DevScene& sc, NodeP W, HotP H,
                                             int xflags, XCounters& cnt) {
     const int lane = threadIdx.x & 63;
     const unsigned n_list = *wk.n_list;
-    // run length k: the largest power of two <= the launch's maximum (xflags bits 8-10: log2, from
+    // run length k: the largest power of two <= the launch's maximum (xflags' XF_RUN bits: log2, from
     // GI_X_MAX_RUN or the environment variable of that name) and <= spp that still leaves about
     // GI_X_UNITS_PER_LANE units per lane of the grid (every wave computes the same k)
     int k = 1;
     {
         const double lanes = (double)gridDim.x * (double)blockDim.x;
         const double samples = (double)n_list * (double)(wk.s1 - wk.s0);
-        const int max_run = 1 << ((xflags >> 8) & 7);
+        const int max_run = 1 << ((xflags >> XF_RUN_SHIFT) & XF_RUN_MASK);
         while (2 * k <= max_run && 2 * k <= wk.s1 - wk.s0 && samples / (2.0 * k) >= GI_X_UNITS_PER_LANE * lanes) k *= 2;
     }
     const unsigned runs = (unsigned)((wk.s1 - wk.s0 + k - 1) / k);    // units per pixel (run c: samples s0 + c k ...)
     const unsigned n_groups = (n_list + 63u) >> 6;
-    // xflags bit 5 (pixel-major blocks, launches of >= 64 units per pixel): a block is ONE pixel's
+    // XF_PIXEL_MAJOR (pixel-major blocks, launches of >= 64 units per pixel): a block is ONE pixel's
     // 64 consecutive runs instead of 64 pixels' run c, so a wave's lanes start on the same pixel's
     // samples -- nearly the same primary ray -- and walk the same nodes together
-    const bool pm = (xflags & 32) != 0 && runs >= 64u;
+    const bool pm = (xflags & XF_PIXEL_MAJOR) != 0 && runs >= 64u;
     const unsigned rpb = (runs + 63u) >> 6;   // (pm) blocks per pixel
     const unsigned n_blocks = pm ? n_list * rpb : n_groups * runs;
-    // xflags bit 4 (spread): group g holds list entries g, g + G, g + 2G, ... (G groups) instead of
+    // XF_SPREAD: group g holds list entries g, g + G, g + 2G, ... (G groups) instead of
     // 64 consecutive ones, so a wave's 64 pixels come from all over the frame: the expensive pixels
     // of a frame cluster in space (the soup's core), and consecutive entries would give all of them
     // to a few waves, whose lanes then pace each other (every loop iteration waits for the others'
     // shading) while the rest of the chip idles.  Spread, each long path shares its wave with
     // cheap ones that finish early (fast iterations, idle lanes for its shadow rays).
-    const bool spread = (xflags & 16) != 0;
+    const bool spread = (xflags & XF_SPREAD) != 0;
     // the wave's current block lives in its LDS row: blk_list[0..63] = the group's list entries,
     // blk_meta = {units handed out, group, run}; lanes that do not run the handler keep no copy
     unsigned* blk_meta = blk_list + 64;
     if (lane == 0) { blk_meta[0] = 64u; blk_meta[3] = 0u; }
     __builtin_amdgcn_wave_barrier();
-    const bool inline_shadow = (xflags & 1) != 0;
-    const bool no_shadow = (xflags & 4) != 0;   // GI_FLAG_X_NO_SHADOW (tests): every light visible
-    const bool handoff = HELP && (xflags & 8) != 0 && !no_shadow;
+    const bool inline_shadow = (xflags & XF_INLINE_SHADOW) != 0;
+    const bool no_shadow = (xflags & XF_NO_SHADOW) != 0;   // GI_FLAG_X_NO_SHADOW (tests): every light visible
+    const bool handoff = HELP && (xflags & XF_HANDOFF) != 0 && !no_shadow;
     const int tid = threadIdx.x, wbase = tid & ~63;
     if (HELP) {
         hp_.own[tid] = -1;
@@ -2025,16 +2025,17 @@ __device__ __forceinline__ void mode_x_wave(const DevScene& sc, NodeP W, HotP H,
 // LDS: small scenes (sc.x_lds_bytes > 0) keep the whole traversal structure -- wide nodes and
 // leaf records -- in LDS, copied once by each resident workgroup; every traversal load is then a
 // ds_read instead of a vector-memory round trip.
-// W4: 4 waves per SIMD (<= 128 VGPRs) for LDS-resident scenes whose shading is light (triangles
-// without acos texture mapping: +7% on the Cornell box); scenes with spheres / cones / rectangles
-// keep 3 (their heavier handler spills at 128 VGPRs: -45% on the main.cpp scene at 4).
-// For HBM-resident scenes (!LDS) W4 selects the shadow-ray handoff build (XHelp): chosen
-// per launch for small launches, whose frame time is their longest paths' latency (C4: 3.01 ->
-// 2.64 ms, with spread work groups 2.40 ms); in long launches (C5) the handoff build's heavier code
-// costs 8%, so they run without.
+// W4, LDS-resident scenes (XVariant::w4): 4 waves per SIMD (<= 128 VGPRs) for scenes whose shading is
+// light (triangles without acos texture mapping: +7% on the Cornell box); scenes with spheres / cones /
+// rectangles keep 3 (their heavier handler spills at 128 VGPRs: -45% on the main.cpp scene at 4).
+// W4, HBM-resident scenes (XVariant::help): the same template parameter selects the shadow-ray handoff
+// build (XHelp), chosen per launch for small launches, whose frame time is their longest paths' latency
+// (C4: 3.01 -> 2.64 ms, with spread work groups 2.40 ms); in long launches (C5) the handoff build's
+// heavier code costs 8%, so they run without.
 // CN (HBM-resident scenes): traverse the quantised nodes (DevScene::xcnodes) instead of XWNode.
 // TR (HBM-resident scenes): the scene is triangle meshes of the 4-wave kinds only (DevScene::x_tri_only,
-// e.g. the 100k soup): mode_x_wave's TRI specialisation
+// e.g. the 100k soup): mode_x_wave's TRI specialisation (LDS-resident scenes: theirs is W4).
+// x_dispatch (below) names the instantiations that are launched: LDS, W4 x SH; HBM, HELP x CN x SH x TR.
 template <bool STATS, bool LDS, bool W4, bool CN, bool SH, bool TR = false>
 __global__ __launch_bounds__(256, (LDS && W4) ? GI_X_MIN_WAVES_LDS : GI_X_MIN_WAVES) void k_mode_x(DevScene sc, CamDev cam, V3 light, TileMap m, int spp, int depth,
                                                  uint64_t seed, double* rgb, uint8_t* rgb8,
@@ -2044,30 +2045,14 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_X_MIN_WAVES_LDS : GI_X_MIN_WA
     unsigned* blk = s_blk[threadIdx.x >> 6];
     if (LDS) {
         extern __shared__ int4 lds_scene[];
-        // traversal records and shading records (primitives, entities): the shading handler then
-        // issues no global load, so its waits never include the lane's outstanding stores
-        const int nw = sc.n_xwnodes * (int)(sizeof(XWNode) / sizeof(int4));
-        const int nh = sc.n_xhot * (int)(sizeof(XHot) / sizeof(int4));
-        const int np = sc.n_xprims * (int)(sizeof(XPrim) / sizeof(int4));
-        const int ne = sc.n_ents * (int)(sizeof(REnt) / sizeof(int4));
-        const int4* gw = reinterpret_cast<const int4*>(sc.xwnodes);
-        const int4* gh = reinterpret_cast<const int4*>(sc.xhot);
-        const int4* gp = reinterpret_cast<const int4*>(sc.xprims);
-        const int4* ge = reinterpret_cast<const int4*>(sc.ents);
-        for (int i = threadIdx.x; i < nw; i += blockDim.x) lds_scene[i] = gw[i];
-        for (int i = threadIdx.x; i < nh; i += blockDim.x) lds_scene[nw + i] = gh[i];
-        for (int i = threadIdx.x; i < np; i += blockDim.x) lds_scene[nw + nh + i] = gp[i];
-        for (int i = threadIdx.x; i < ne; i += blockDim.x) lds_scene[nw + nh + np + i] = ge[i];
-        __syncthreads();
-        const XWNode* W = reinterpret_cast<const XWNode*>(lds_scene);
-        const XHot* H = reinterpret_cast<const XHot*>(lds_scene + nw);
-        const XPrim* XP = reinterpret_cast<const XPrim*>(lds_scene + nw + nh);
-        const REnt* EN = reinterpret_cast<const REnt*>(lds_scene + nw + nh + np);
+        // traversal records and shading records (primitives, entities) staged in LDS: the shading handler
+        // then issues no global load, so its waits never include the lane's outstanding stores
+        const XStaged s = x_stage_lds<false>(sc, lds_scene);
         // 4-wave kernel: path values used only by the shading handler and at the shadow ray's end
         // (occluded sum, next direction, throughput T, RNG key) live in a per-lane LDS slot after
         // the scene instead of in VGPRs / scratch
-        double* pslot = reinterpret_cast<double*>(lds_scene + nw + nh + np + ne) + 10 * threadIdx.x;
-        mode_x_wave<STATS, true, W4, false, false, SH, W4>(sc, W, H, XP, EN, pslot, nullptr, XHelp{},
+        double* pslot = reinterpret_cast<double*>(s.end) + 10 * threadIdx.x;
+        mode_x_wave<STATS, true, W4, false, false, SH, W4>(sc, s.W, s.H, s.XP, s.EN, pslot, nullptr, XHelp{},
                                                                         cam, light, m, spp, depth, seed, rgb, rgb8, blk,
                                                                         wk, handle8, xflags, c);
     } else {
@@ -2308,11 +2293,11 @@ const XEnv& x_env() {
 }
 
 // wavefront Mode X (gi_wf.hip)
-hipError_t launch_wf(const DevScene& sc, int kv, size_t lds_bytes, int resident, int form, const CamDev& cam, V3 light,
+hipError_t launch_wf(const DevScene& sc, XVariant var, size_t lds_bytes, int resident, int form, const CamDev& cam, V3 light,
                      int w, int h, int y0, const gi_opts& o, double* rgb, uint8_t* rgb8, const XScratch& xs,
                      const unsigned* n_list_dev, unsigned long long* stats, int xflags, hipStream_t stream,
                      hipEvent_t ev_begin, hipEvent_t ev_end);
-hipError_t wf_occupancy(const DevScene& sc, int kv, bool flat, size_t lds_bytes, int form, int* per_cu);
+hipError_t wf_occupancy(const DevScene& sc, XVariant var, bool flat, size_t lds_bytes, int form, int* per_cu);
 size_t wf_slot_bytes();
 size_t wf_scene_lds_bytes(const DevScene& sc);
 
@@ -2335,7 +2320,7 @@ int x_form_choice(const DevScene& sc, const XLaunchCfg& xc, const gi_opts& o) {
     if (env.wf >= 0) return env.wf == 1 ? (o.depth <= GI_WF_MAX_DEPTH ? 1 : 0) : env.wf == 2 ? 2 : 0;
     // small HBM-resident trees (<= 1 MB of wide nodes: L2-resident, short traversals -- X-zoo 5.7 ->
     // 4.8-5.0 ms, the 1k soup even) run k_seg too
-    return (xc.kv >= 2 || (size_t)sc.n_xwnodes * sizeof(XWNode) <= ((size_t)1 << 20)) ? 2 : 0;
+    return (xc.var.lds || (size_t)sc.n_xwnodes * sizeof(XWNode) <= ((size_t)1 << 20)) ? 2 : 0;
 }
 long long x_wf_chunk() { return 8ll << 20; }   // wavefront Mode X: units (pixel samples) per chunk = queue capacity
 int x_env_rf_per_slot() { return x_env().rf_per_slot; }
@@ -2355,30 +2340,47 @@ int r_kernel_choice(const DevScene& sc, const gi_opts& o) {
     return (env.r_flat == 2 || (unsigned)sc.n_ents > kRfEntMask) ? 2 : 1;
 }
 
+// The k_mode_x instantiation a launch runs: f(XTag) for the scene and the variant.  LDS-resident scenes:
+// W4 x SH; HBM-resident ones: HELP x CN x SH x TR -- with STATS the 40 instantiations of the library.
+// SH: the per-level masks in one 64-bit word when the tree has at most 8 levels.
+template <typename F>
+void x_dispatch(const DevScene& sc, XVariant var, bool stats, F&& f) {
+    const bool sh = sc.x_max_depth <= 7;
+    if (var.lds)
+        with_bools([&](auto S, auto W, auto H) { f(XTag<S.value, true, W.value, false, H.value, false, false, false>{}); },
+                   stats, var.w4, sh);
+    else
+        with_bools([&](auto S, auto HP, auto C, auto H, auto T) { f(XTag<S.value, false, false, HP.value, H.value, T.value, C.value, false>{}); },
+                   stats, var.help, sc.xcnodes != nullptr, sh, sc.x_tri_only != 0);
+}
+// (k_mode_x's W4 parameter carries XVariant::w4 or XVariant::help: see the kernel's comment)
+template <typename V>
+constexpr auto x_kernel(V) {
+    return &k_mode_x<V::stats, V::lds, V::lds ? V::w4 : V::help, V::cn, V::sh, V::tri>;
+}
+
 hipError_t x_launch_config(const DevScene& sc, int device, XLaunchCfg& cfg) {
     const bool lds = sc.x_lds_bytes > 0;
     cfg.lds_bytes = lds ? (size_t)sc.x_lds_bytes + (sc.x_waves4 ? 256 * 10 * sizeof(double) : 0)
                         : 16 * 256 * sizeof(int) + 256 * (7 * sizeof(double) + 2 * sizeof(int));
-    cfg.kv = 2 * (int)lds + ((lds && sc.x_waves4) ? 1 : 0);   // 0 / 1 (per launch, HELP): HBM-resident
+    cfg.var.lds = lds;
+    cfg.var.w4 = lds && sc.x_waves4;
     int cus = 0, per_cu = 0;
     hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
     if (e != hipSuccess) return e;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &per_cu, cfg.kv == 3 ? reinterpret_cast<const void*>(k_mode_x<false, true, true, false, false>)
-                 : cfg.kv == 2 ? reinterpret_cast<const void*>(k_mode_x<false, true, false, false, false>)
-                 : sc.xcnodes  ? (sc.x_tri_only ? reinterpret_cast<const void*>(k_mode_x<false, false, false, true, false, true>)
-                                                : reinterpret_cast<const void*>(k_mode_x<false, false, false, true, false>))
-                 : sc.x_tri_only ? reinterpret_cast<const void*>(k_mode_x<false, false, false, false, false, true>)
-                               : reinterpret_cast<const void*>(k_mode_x<false, false, false, false, false>),
-        64 * kWavesPerBlock, cfg.lds_bytes);
+    // the scene's own instantiation, STATS and handoff off (neither moves the occupancy: DESIGN.md §5)
+    x_dispatch(sc, cfg.var, false, [&](auto V) {
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(x_kernel(V)), 64 * kWavesPerBlock,
+                                                         cfg.lds_bytes);
+    });
     if (e != hipSuccess) return e;
     cfg.resident = std::max(1, cus) * std::max(1, per_cu);
     cfg.wf_lds_bytes = (lds ? wf_scene_lds_bytes(sc) : 16 * 256 * sizeof(int)) + wf_slot_bytes();
-    const bool flat = sc.x_flat && x_env().flat;   // (the launches' choice: launch_render's bit 6)
-    e = wf_occupancy(sc, cfg.kv, flat, cfg.wf_lds_bytes, 1, &per_cu);
+    const bool flat = sc.x_flat && x_env().flat;   // (the launches' choice: launch_render's XF_NO_FLAT)
+    e = wf_occupancy(sc, cfg.var, flat, cfg.wf_lds_bytes, 1, &per_cu);
     if (e != hipSuccess) return e;
     cfg.wf_resident = std::max(1, cus) * std::max(1, per_cu);
-    e = wf_occupancy(sc, cfg.kv, flat, cfg.wf_lds_bytes, 2, &per_cu);
+    e = wf_occupancy(sc, cfg.var, flat, cfg.wf_lds_bytes, 2, &per_cu);
     if (e != hipSuccess) return e;
     cfg.seg_resident = std::max(1, cus) * std::max(1, per_cu);
     return hipSuccess;
@@ -2420,31 +2422,24 @@ hipError_t launch_render(const DevScene& sc, const XLaunchCfg& xc, const CamDev&
             const dim3 bgrid((unsigned)std::min<long long>(2 * m.n_local, 2048));
             const dim3 hgrid(16384);   // k_rf_hit: persistent waves (one per workgroup) over the segments
             const int rgroup = x_env().rf_group;
-            if (stats) hipLaunchKernelGGL(k_rf_walk<true>, pgrid, block, 0, stream, sc, cam, m, tau, f, st);
-            else hipLaunchKernelGGL(k_rf_walk<false>, pgrid, block, 0, stream, sc, cam, m, tau, f, st);
-#define GI_LAUNCH_RF(S, T)                                                                                                \
-    do {                                                                                                                  \
-        hipLaunchKernelGGL(k_rf_scan, dim3(1), dim3(1024), 0, stream, f.rcnt, f.soff, nullptr, m.n_local, GI_RF_SEG);    \
-        hipLaunchKernelGGL((k_rf_hit<S, T>), hgrid, dim3(64), 0, stream, sc, cam, m, f, st);                              \
-        hipLaunchKernelGGL(k_rf_scan, dim3(1), dim3(1024), 0, stream, f.shc, f.hoff, f.soff + m.n_local, 0ll, 1u);       \
-        hipLaunchKernelGGL(k_rf_reach<S>, dim3(4 * fgrid.x), dim3(64), 0, stream, sc, cam, m, f, st, rgroup);              \
-        hipLaunchKernelGGL((k_rf_shade<S, T>), pgrid, block, 0, stream, sc, cam, light, m, rgb, rgb8, f, st);             \
-        hipLaunchKernelGGL((k_mode_r_batch<S, T>), bgrid, block, 0, stream, sc, cam, light, m, rgb, rgb8, st, tau,        \
-                           (const unsigned*)xs.rf_ovf, (const unsigned*)(xs.rf_cnt + 1));                                 \
-    } while (0)
-            if (stats) { if (tri) GI_LAUNCH_RF(true, true); else GI_LAUNCH_RF(true, false); }
-            else { if (tri) GI_LAUNCH_RF(false, true); else GI_LAUNCH_RF(false, false); }
-#undef GI_LAUNCH_RF
+            with_bools([&](auto S, auto T) {
+                hipLaunchKernelGGL(k_rf_walk<S.value>, pgrid, block, 0, stream, sc, cam, m, tau, f, st);
+                hipLaunchKernelGGL(k_rf_scan, dim3(1), dim3(1024), 0, stream, f.rcnt, f.soff, nullptr, m.n_local, GI_RF_SEG);
+                hipLaunchKernelGGL((k_rf_hit<S.value, T.value>), hgrid, dim3(64), 0, stream, sc, cam, m, f, st);
+                hipLaunchKernelGGL(k_rf_scan, dim3(1), dim3(1024), 0, stream, f.shc, f.hoff, f.soff + m.n_local, 0ll, 1u);
+                hipLaunchKernelGGL(k_rf_reach<S.value>, dim3(4 * fgrid.x), dim3(64), 0, stream, sc, cam, m, f, st, rgroup);
+                hipLaunchKernelGGL((k_rf_shade<S.value, T.value>), pgrid, block, 0, stream, sc, cam, light, m, rgb, rgb8, f, st);
+                hipLaunchKernelGGL((k_mode_r_batch<S.value, T.value>), bgrid, block, 0, stream, sc, cam, light, m, rgb, rgb8, st, tau,
+                                   (const unsigned*)xs.rf_ovf, (const unsigned*)(xs.rf_cnt + 1));
+            }, stats, tri);
         } else if (rk) {   // k_mode_r_batch over the whole frame
             const dim3 sgrid((unsigned)((m.n_local * (kTile * kTile) + 31) / 32));
-            if (stats) { if (tri) hipLaunchKernelGGL((k_mode_r_batch<true, true>), sgrid, block, 0, stream, sc, cam, light, m, rgb, rgb8, st, tau, nullptr, nullptr);
-                         else hipLaunchKernelGGL((k_mode_r_batch<true, false>), sgrid, block, 0, stream, sc, cam, light, m, rgb, rgb8, st, tau, nullptr, nullptr); }
-            else { if (tri) hipLaunchKernelGGL((k_mode_r_batch<false, true>), sgrid, block, 0, stream, sc, cam, light, m, rgb, rgb8, st, tau, nullptr, nullptr);
-                   else hipLaunchKernelGGL((k_mode_r_batch<false, false>), sgrid, block, 0, stream, sc, cam, light, m, rgb, rgb8, st, tau, nullptr, nullptr); }
-        } else if (stats) {
-            hipLaunchKernelGGL(k_mode_r<true>, grid, block, 0, stream, sc, cam, light, m, rgb, rgb8, st, tau, dfs);
+            with_bools([&](auto S, auto T) {
+                hipLaunchKernelGGL((k_mode_r_batch<S.value, T.value>), sgrid, block, 0, stream, sc, cam, light, m, rgb, rgb8, st, tau, nullptr, nullptr);
+            }, stats, tri);
         } else {
-            hipLaunchKernelGGL(k_mode_r<false>, grid, block, 0, stream, sc, cam, light, m, rgb, rgb8, st, tau, dfs);
+            with_bools([&](auto S) { hipLaunchKernelGGL(k_mode_r<S.value>, grid, block, 0, stream, sc, cam, light, m, rgb, rgb8, st, tau, dfs); },
+                       stats);
         }
         mark(ev_end);
     } else {
@@ -2456,10 +2451,8 @@ hipError_t launch_render(const DevScene& sc, const XLaunchCfg& xc, const CamDev&
         // at most 32 samples per resident lane -- their time is the longest paths' latency and lanes
         // run out of work early (C4: 10 per lane; X-soup1000, 169 per lane, is throughput-bound and
         // 25% slower spread)
-        const bool help = xc.kv == 0 && env.help &&
-                          n_slots * (long long)o.spp <= 32ll * 256ll * (long long)xc.resident;
-        const int kv = xc.kv + (help ? 1 : 0);
-        const size_t lds_bytes = xc.lds_bytes;
+        XVariant var = xc.var;
+        var.help = !var.lds && env.help && n_slots * (long long)o.spp <= 32ll * 256ll * (long long)xc.resident;
         // up to one lane per (pixel slot, sample): single-sample units can occupy that many lanes
         const long long want = (n_slots * (long long)o.spp / 64 + kWavesPerBlock - 1) / kWavesPerBlock;
         const dim3 pgrid((unsigned)std::max<long long>(1, std::min<long long>(want, xc.resident)));
@@ -2485,55 +2478,30 @@ hipError_t launch_render(const DevScene& sc, const XLaunchCfg& xc, const CamDev&
         const int form = x_form_choice(sc, xc, o);
         unsigned* zero2 = form == 2 ? xs.wcnt : nullptr;   // k_seg's unit counter, zeroed by the classify pass
         unsigned* cl = cont ? nullptr : xs.list;
-        if (stats) hipLaunchKernelGGL(k_x_classify<true>, cgrid, dim3(kClassifyBlock), 0, stream, sc, cam, m, s1 - s0, rgb, rgb8, cl, sc.work + 1, st, zero2);
-        else hipLaunchKernelGGL(k_x_classify<false>, cgrid, dim3(kClassifyBlock), 0, stream, sc, cam, m, s1 - s0, rgb, rgb8, cl, sc.work + 1, st, zero2);
+        with_bools([&](auto S) {
+            hipLaunchKernelGGL(k_x_classify<S.value>, cgrid, dim3(kClassifyBlock), 0, stream, sc, cam, m, s1 - s0, rgb, rgb8, cl, sc.work + 1, st, zero2);
+        }, stats);
         // shading-handler threshold (eighths of the live lanes that must wait): the builder's
         // estimate for the scene (DevScene::x_handle8)
         const int h8 = sc.x_handle8;
-        // schedule flags (bit 0: inline shadow, bit 2: no shadow rays, bit 3: shadow handoff, bit 4:
-        // spread work groups -- with the handoff build, bit 5: pixel-major work blocks, bit 6: gi_wf.hip's
-        // forms walk the tree although the flat leaf table applies, GI_X_FLAT=0) and the maximum run
-        // length (log2, bits 8-10)
-        const int xf = sc.x_flags | (env.run_log2 << 8) | ((o.flags & GI_FLAG_X_NO_SHADOW) ? 4 : 0) | (env.help ? 8 : 0) |
-                       (help ? 16 : 0) | 32 | (env.flat ? 0 : 64);
+        // schedule flags (XFlag, gi_scene.h): the scene's, the launch's and the maximum run length (log2)
+        const int xf = sc.x_flags | (env.run_log2 << XF_RUN_SHIFT) | ((o.flags & GI_FLAG_X_NO_SHADOW) ? XF_NO_SHADOW : 0) |
+                       (env.help ? XF_HANDOFF : 0) | (var.help ? XF_SPREAD : 0) | XF_PIXEL_MAJOR | (env.flat ? 0 : XF_NO_FLAT);
         if (form) {   // gi_wf.hip's forms, timed as one pass
             if (!xs.wcnt || (form == 1 && (!xs.wq[0] || !xs.wq[1] || xs.wcap <= 0))) return hipErrorInvalidValue;
-            e = launch_wf(sc, xc.kv, xc.wf_lds_bytes, form == 2 ? xc.seg_resident : xc.wf_resident, form, cam, light, w, h, y0,
+            e = launch_wf(sc, xc.var, xc.wf_lds_bytes, form == 2 ? xc.seg_resident : xc.wf_resident, form, cam, light, w, h, y0,
                           o, rgb, rgb8, xs, sc.work + 1, stats ? st : nullptr, xf, stream, ev_begin, ev_end);
             if (e != hipSuccess) return e;
             if (o.spp > 1) hipLaunchKernelGGL(k_x_reduce, sgrid, dim3(256), 0, stream, m, wk, o.spp, rgb, rgb8);
             if (timed) kt->recorded++;
             return hipGetLastError();
         }
-        const bool cn = kv < 2 && sc.xcnodes != nullptr;
-#define GI_LAUNCH_X2(S, L, W, SH, TR) hipLaunchKernelGGL((k_mode_x<S, L, W, false, SH, TR>), pgrid, block, lds_bytes, stream, sc, cam, light, m, o.spp, \
-                                           o.depth, o.seed, rgb, rgb8, st, wk, h8, xf)
-#define GI_LAUNCH_XC2(S, W, SH, TR) hipLaunchKernelGGL((k_mode_x<S, false, W, true, SH, TR>), pgrid, block, lds_bytes, stream, sc, cam, light, m, \
-                                          o.spp, o.depth, o.seed, rgb, rgb8, st, wk, h8, xf)
-        // TR: triangle-only HBM-resident scenes (the LDS kernels do not use it: theirs is W4)
-#define GI_LAUNCH_X1(S, L, W, SH) do { if (!(L) && sc.x_tri_only) GI_LAUNCH_X2(S, L, W, SH, true); else GI_LAUNCH_X2(S, L, W, SH, false); } while (0)
-#define GI_LAUNCH_XC1(S, W, SH) do { if (sc.x_tri_only) GI_LAUNCH_XC2(S, W, SH, true); else GI_LAUNCH_XC2(S, W, SH, false); } while (0)
-        // SH: the per-level masks in one 64-bit word when the tree has at most 8 levels
-        const bool sh = sc.x_max_depth <= 7;
-#define GI_LAUNCH_X(S, L, W) do { if (sh) GI_LAUNCH_X1(S, L, W, true); else GI_LAUNCH_X1(S, L, W, false); } while (0)
-#define GI_LAUNCH_XC(S, W) do { if (sh) GI_LAUNCH_XC1(S, W, true); else GI_LAUNCH_XC1(S, W, false); } while (0)
         mark(ev_begin);
-        if (stats) {
-            if (kv == 3) GI_LAUNCH_X(true, true, true); else if (kv == 2) GI_LAUNCH_X(true, true, false);
-            else if (cn) { if (kv == 1) GI_LAUNCH_XC(true, true); else GI_LAUNCH_XC(true, false); }
-            else if (kv == 1) GI_LAUNCH_X(true, false, true); else GI_LAUNCH_X(true, false, false);
-        } else {
-            if (kv == 3) GI_LAUNCH_X(false, true, true); else if (kv == 2) GI_LAUNCH_X(false, true, false);
-            else if (cn) { if (kv == 1) GI_LAUNCH_XC(false, true); else GI_LAUNCH_XC(false, false); }
-            else if (kv == 1) GI_LAUNCH_X(false, false, true); else GI_LAUNCH_X(false, false, false);
-        }
+        x_dispatch(sc, var, stats, [&](auto V) {
+            hipLaunchKernelGGL(x_kernel(V), pgrid, block, xc.lds_bytes, stream, sc, cam, light, m, o.spp, o.depth, o.seed, rgb, rgb8, st, wk,
+                               h8, xf);
+        });
         mark(ev_end);
-#undef GI_LAUNCH_X
-#undef GI_LAUNCH_XC
-#undef GI_LAUNCH_X1
-#undef GI_LAUNCH_XC1
-#undef GI_LAUNCH_X2
-#undef GI_LAUNCH_XC2
         if (o.spp > 1) hipLaunchKernelGGL(k_x_reduce, sgrid, dim3(256), 0, stream, m, wk, o.spp, rgb, rgb8);
     }
     if (timed) kt->recorded++;
@@ -2554,33 +2522,33 @@ hipError_t launch_box_kat(int n, const double* recs, int32_t* out, hipStream_t s
 }
 
 // gi_kat_x_query: the variant, the flat choice and the dynamic LDS of a k_seg launch on this scene
-// (launch_render's xc.kv, xc.wf_lds_bytes and bit 6).  flags bit 0: the tree walk where the flat
-// table would apply (GI_X_FLAT=0 in process); bit 1: the HBM-resident variants (kv = 0: the level
+// (launch_render's xc.var, xc.wf_lds_bytes and XF_NO_FLAT).  flags bit 0: the tree walk where the flat
+// table would apply (GI_X_FLAT=0 in process); bit 1: the HBM-resident variants (the level
 // stack instead of the staged scene) for a scene that would be staged in LDS.
-hipError_t launch_x_query_kat(const DevScene& sc, int kv, bool flat, size_t lds_bytes, V3 cam_pos, int n,
+hipError_t launch_x_query_kat(const DevScene& sc, XVariant var, bool flat, size_t lds_bytes, V3 cam_pos, int n,
                               const double* recs, int32_t* oi, double* od, hipStream_t stream);
-void wf_variant(const DevScene& sc, int kv, bool flat, int32_t out[6]);
+void wf_variant(const DevScene& sc, XVariant var, bool flat, int32_t out[6]);
 namespace {
 struct XQueryCfg {
-    int kv;
+    XVariant var;
     size_t lds_bytes;
     bool flat;
 };
 XQueryCfg x_query_cfg(const XLaunchCfg& xc, int flags) {
-    const bool hbm = (flags & 2) != 0 && xc.kv >= 2;
-    return XQueryCfg{hbm ? 0 : xc.kv, hbm ? 16 * 256 * sizeof(int) + wf_slot_bytes() : xc.wf_lds_bytes,
+    const bool hbm = (flags & 2) != 0 && xc.var.lds;
+    return XQueryCfg{hbm ? XVariant{} : xc.var, hbm ? 16 * 256 * sizeof(int) + wf_slot_bytes() : xc.wf_lds_bytes,
                      x_env().flat && (flags & 1) == 0};
 }
 }  // namespace
 hipError_t launch_x_query(const DevScene& sc, const XLaunchCfg& xc, V3 cam_pos, int flags, int n, const double* recs,
                           int32_t* oi, double* od, hipStream_t stream) {
     const XQueryCfg c = x_query_cfg(xc, flags);
-    return launch_x_query_kat(sc, c.kv, c.flat, c.lds_bytes, cam_pos, n, recs, oi, od, stream);
+    return launch_x_query_kat(sc, c.var, c.flat, c.lds_bytes, cam_pos, n, recs, oi, od, stream);
 }
 // the kernel variant (LDS, W4, SH, TRI, CN, FLAT) that launch runs -- with flags 0, k_seg's for this scene
 void x_query_variant(const DevScene& sc, const XLaunchCfg& xc, int flags, int32_t out[6]) {
     const XQueryCfg c = x_query_cfg(xc, flags);
-    wf_variant(sc, c.kv, c.flat, out);
+    wf_variant(sc, c.var, c.flat, out);
 }
 
 hipError_t launch_trace_ray(const DevScene& sc, V3 o, V3 d, V3 light, int32_t* out_i, double* out_d, hipStream_t stream) {

@@ -9,6 +9,7 @@
 // XPrim[] shading records).
 #pragma once
 #include <stdint.h>
+#include <type_traits>
 #include <vector>
 
 #include "gi_math.h"
@@ -222,7 +223,7 @@ struct DevScene {
     int32_t n_rnodes, n_ents, n_xwnodes, n_xprims;
     int32_t x_max_depth;
     int32_t x_handle8;     // Mode X shading-handler threshold, eighths of the live lanes (set at upload)
-    int32_t x_flags;       // Mode X schedule flags: bit 0 = continue paths from shadow rays in traversal
+    int32_t x_flags;       // Mode X schedule flags (XFlag): XF_INLINE_SHADOW or 0
     int32_t n_xhot;
     int32_t x_lds_bytes;   // > 0: xwnodes + xhot fit in LDS and are staged there by each workgroup
     int32_t x_waves4;      // LDS-resident scene with light shading: k_mode_x at 4 waves per SIMD
@@ -299,10 +300,43 @@ struct XScratch {
                                // that many or more; such frames render through k_mode_r_batch
 };
 
+// The Mode X kernels' xflags argument: the scene's schedule flags (DevScene::x_flags) and the launch's.
+enum XFlag : int {
+    XF_INLINE_SHADOW = 1 << 0,   // k_mode_x continues paths from shadow rays in traversal (the builder's choice)
+    XF_NO_SHADOW = 1 << 2,       // GI_FLAG_X_NO_SHADOW (tests): no shadow rays, every light visible
+    XF_HANDOFF = 1 << 3,         // the shadow-ray handoff is allowed (GI_X_HELP; used by the HELP builds)
+    XF_SPREAD = 1 << 4,          // spread work groups (launches that run the handoff build)
+    XF_PIXEL_MAJOR = 1 << 5,     // pixel-major work blocks
+    XF_NO_FLAT = 1 << 6,         // GI_X_FLAT=0: gi_wf.hip's forms walk the tree although the flat leaf table applies
+    XF_RUN_SHIFT = 8, XF_RUN_MASK = 7,   // bits 8-10: log2 of the maximum run length (GI_X_MAX_RUN)
+};
+
+// The run-time choices that pick a Mode X kernel instantiation besides the scene's own properties.
+struct XVariant {
+    bool lds = false;    // the scene is staged in LDS (DevScene::x_lds_bytes > 0)
+    bool w4 = false;     // ... and its shading is light: 4 waves per SIMD (DevScene::x_waves4)
+    bool help = false;   // per launch, HBM-resident scenes, k_mode_x: the shadow-ray handoff build
+};
+// A kernel instantiation as a type: what the dispatchers (x_dispatch, wf_dispatch) hand to their callers.
+template <bool STATS, bool LDS, bool W4, bool HELP, bool SH, bool TRI, bool CN, bool FLAT>
+struct XTag {
+    static constexpr bool stats = STATS, lds = LDS, w4 = W4, help = HELP, sh = SH, tri = TRI, cn = CN, flat = FLAT;
+};
+// f(std::bool_constant<b>...) for run-time booleans b...
+template <bool... Bs, typename F>
+void with_bools(F&& f) {
+    f(std::integral_constant<bool, Bs>{}...);
+}
+template <bool... Bs, typename F, typename... R>
+void with_bools(F&& f, bool b, R... r) {
+    if (b) with_bools<Bs..., true>(f, r...);
+    else with_bools<Bs..., false>(f, r...);
+}
+
 // Mode X launch configuration, computed once per scene when it is created (gi_capi.cpp, on the
 // scene's device): kernel variant, dynamic LDS bytes and the resident persistent grid.
 struct XLaunchCfg {
-    int kv = 0;              // kernel variant: 2 * (LDS-resident scene) + (4 waves per SIMD)
+    XVariant var;            // kernel variant (help is set per launch)
     size_t lds_bytes = 0;    // dynamic LDS per workgroup
     int resident = 1;        // resident 256-thread workgroups on the device (occupancy x CUs)
     size_t wf_lds_bytes = 0; // wavefront Mode X (k_wf_bounce, k_seg): dynamic LDS per workgroup

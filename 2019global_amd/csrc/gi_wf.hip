@@ -209,10 +209,8 @@ __device__ __forceinline__ int wf_trace(float far_r, NodeP W, HotP H, V3 o, V3 d
 #define GI_XFLAT_UNROLL 4   // Phase A records in flight (their loads overlap the previous records' tests)
 #endif
 typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
-#ifndef GI_XFLAT_LDS
-#define GI_XFLAT_LDS 0   // (A/B builds) 1: phase A reads a copy of the table staged in LDS, a broadcast read per record
-#endif
 // record k's eight words from the constant address space: a scalar load at a uniform address
+// (GI_XFLAT_LDS, gi_dev.h: from the table's copy staged in LDS, a broadcast read per record)
 __device__ __forceinline__ u32x8 flat_rec_uniform(const XFlatLeaf* tab, int k) {
 #if GI_XFLAT_LDS
     const int4* q = reinterpret_cast<const int4*>(tab + k);
@@ -376,32 +374,9 @@ __device__ __forceinline__ WFView wf_stage(const DevScene& sc, int4* lds_dyn) {
     v.EN = sc.ents;
     v.FT = sc.xflat;
     if constexpr (LDS) {
-        const int nw = sc.n_xwnodes * (int)(sizeof(XWNode) / sizeof(int4));
-        const int nh = sc.n_xhot * (int)(sizeof(XHot) / sizeof(int4));
-        const int np = sc.n_xprims * (int)(sizeof(XPrim) / sizeof(int4));
-        const int ne = sc.n_ents * (int)(sizeof(REnt) / sizeof(int4));
-        const int4* gw = reinterpret_cast<const int4*>(sc.xwnodes);
-        const int4* gh = reinterpret_cast<const int4*>(sc.xhot);
-        const int4* gp = reinterpret_cast<const int4*>(sc.xprims);
-        const int4* ge = reinterpret_cast<const int4*>(sc.ents);
-        for (int i = threadIdx.x; i < nw; i += blockDim.x) lds_dyn[i] = gw[i];
-        for (int i = threadIdx.x; i < nh; i += blockDim.x) lds_dyn[nw + i] = gh[i];
-        for (int i = threadIdx.x; i < np; i += blockDim.x) lds_dyn[nw + nh + i] = gp[i];
-        for (int i = threadIdx.x; i < ne; i += blockDim.x) lds_dyn[nw + nh + np + i] = ge[i];
-#if GI_XFLAT_LDS
-        const int nf = sc.n_xflat * (int)(sizeof(XFlatLeaf) / sizeof(int4));
-        const int4* gf = reinterpret_cast<const int4*>(sc.xflat);
-        for (int i = threadIdx.x; i < nf; i += blockDim.x) lds_dyn[nw + nh + np + ne + i] = gf[i];
-        v.FT = reinterpret_cast<const XFlatLeaf*>(lds_dyn + nw + nh + np + ne);
-#else
-        const int nf = 0;
-#endif
-        __syncthreads();
-        v.LW = reinterpret_cast<const XWNode*>(lds_dyn);
-        v.LH = reinterpret_cast<const XHot*>(lds_dyn + nw);
-        v.XP = reinterpret_cast<const XPrim*>(lds_dyn + nw + nh);
-        v.EN = reinterpret_cast<const REnt*>(lds_dyn + nw + nh + np);
-        v.pl = reinterpret_cast<double*>(lds_dyn + nw + nh + np + ne + nf) + threadIdx.x;
+        const XStaged s = x_stage_lds<GI_XFLAT_LDS != 0>(sc, lds_dyn);
+        v.LW = s.W; v.LH = s.H; v.XP = s.XP; v.EN = s.EN; v.FT = s.FT;
+        v.pl = reinterpret_cast<double*>(s.end) + threadIdx.x;
     } else {
         v.nst = reinterpret_cast<int*>(lds_dyn) + threadIdx.x;   // 16 levels x 256 lanes
         v.pl = reinterpret_cast<double*>(reinterpret_cast<int*>(lds_dyn) + 16 * 256) + threadIdx.x;
@@ -465,6 +440,42 @@ __device__ __forceinline__ void wf_wave_steps(uint32_t n, uint64_t& it, uint64_t
     }
     if ((threadIdx.x & 63) == 0) { it += mx; ln += sm; }
 }
+// A segment's query in the kernel variant's form -- the flat leaf table, or the tree walk over the nodes
+// staged in LDS, the quantised nodes or the wide nodes in HBM: the one place that chooses.  ANY: the
+// shadow any-hit before tmax, else the closest hit.  skip: the ray's own plane group (254: none; the
+// quantised nodes carry no groups).
+template <bool ANY, bool LDS, bool SH, bool TRI, bool CN, bool FLAT>
+__device__ __forceinline__ int x_query(const DevScene& sc, const WFView& v, float far_r, const V3& o, const V3& d, double tmax,
+                                       bool act, double& t_out, uint32_t& nnode, uint32_t& nprim, uint32_t& st_steps, int skip) {
+    if constexpr (FLAT) return wf_flat<ANY, TRI>(far_r, v.FT, sc.n_xflat, v.LH, o, d, tmax, act, t_out, nnode, nprim, st_steps, skip);
+    else if constexpr (LDS) return wf_trace<ANY, true, false, SH, TRI, false>(far_r, v.LW, v.LH, o, d, tmax, act, v.nst, t_out, nnode, nprim, st_steps, skip);
+    else if constexpr (CN) return wf_trace<ANY, false, false, SH, TRI, true>(far_r, sc.xcnodes, sc.xhot, o, d, tmax, act, v.nst, t_out, nnode, nprim, st_steps);
+    else return wf_trace<ANY, false, false, SH, TRI, true>(far_r, sc.xwnodes, sc.xhot, o, d, tmax, act, v.nst, t_out, nnode, nprim, st_steps, skip);
+}
+// The own-plane skip of a ray that leaves a surface of plane group pg (254: none) and normal pn along
+// dir: the group, when the ray is steep enough that the exact tests of the group's primitives would
+// all find t below MX_TMIN (gi_build.cpp assign_plane_groups; skip_cos: gi_dev.h x_skip_cos), else 254.
+__device__ __forceinline__ int x_own_plane(int pg, const V3& pn, const V3& dir, double skip_cos) {
+    return (pg < 254 && fabs(dot(dir, pn)) >= skip_cos) ? pg : 254;
+}
+// The frame of a closest hit (prim best at t along o + t d): the point P, the direction Ld and distance
+// ldist to the point light, the primitive's plane group pg and normal pn -- the shadow ray and the
+// next ray leave that plane.  Without a hit: P = o and values that skip nothing.
+struct XHitFrame { V3 P, Ld, pn; double ldist; int pg; };
+__device__ __forceinline__ XHitFrame x_hit_frame(const WFView& v, const V3& light, const V3& o, const V3& d, bool hit, int best, double t) {
+    XHitFrame h{o, v3(0, 0, 1), v3(0, 0, 1), 0.0, 254};
+    if (hit) {
+        h.P = o + t * d;
+        const V3 lv = light - h.P;
+        h.ldist = gsqrt(dot(lv, lv));
+        h.Ld = normalize(lv);
+        const XPrim& px = v.XP[best];
+        h.pg = px.pad[0] < 254 ? px.pad[0] : 254;
+        h.pn = ld3(px.n);
+    }
+    return h;
+}
+
 template <bool STATS, bool LDS, bool SH, bool TRI, bool CN, bool FLAT, typename KeyF>
 __device__ __forceinline__ bool x_segment(const DevScene& sc, const WFView& v, const V3& light, int depth, bool no_shadow, bool act,
                                           const KeyF& id_of, V3& o, V3& d, V3& L, V3& T,
@@ -472,17 +483,12 @@ __device__ __forceinline__ bool x_segment(const DevScene& sc, const WFView& v, c
                                           double skip_cos = 2.0, int* splane = nullptr, float far_r = INFINITY) {
     uint32_t st_steps = 0;
     uint64_t c0 = STATS ? clock64() : 0;
-    V3 P = o, Ld = v3(0, 0, 1);
     bool occl = false;
     // ---- closest hit
     double tbest = INFINITY;
-    int best;
     // the own-plane skip of this ray (k_seg carries it from the previous segment; 254: none)
     const int skip_c = splane ? *splane : 254;
-    if constexpr (FLAT) best = wf_flat<false, TRI>(far_r, v.FT, sc.n_xflat, v.LH, o, d, INFINITY, act, tbest, nnode, nprim, st_steps, skip_c);
-    else if constexpr (LDS) best = wf_trace<false, true, false, SH, TRI, false>(far_r, v.LW, v.LH, o, d, INFINITY, act, v.nst, tbest, nnode, nprim, st_steps, skip_c);
-    else if constexpr (CN) best = wf_trace<false, false, false, SH, TRI, true>(far_r, sc.xcnodes, sc.xhot, o, d, INFINITY, act, v.nst, tbest, nnode, nprim, st_steps);
-    else best = wf_trace<false, false, false, SH, TRI, true>(far_r, sc.xwnodes, sc.xhot, o, d, INFINITY, act, v.nst, tbest, nnode, nprim, st_steps, skip_c);
+    const int best = x_query<false, LDS, SH, TRI, CN, FLAT>(sc, v, far_r, o, d, INFINITY, act, tbest, nnode, nprim, st_steps, skip_c);
     if (act) ++nrays;
     if (STATS) {
         wf_wave_steps(st_steps, ws.it_c, ws.ln_c);
@@ -493,27 +499,12 @@ __device__ __forceinline__ bool x_segment(const DevScene& sc, const WFView& v, c
     }
     const bool hit = act && best >= 0;
     // ---- the hit point and its shadow ray toward the point light
-    double ldist = 0.0;
-    int pg = 254;   // the hit's plane group: the shadow ray and the next ray leave its plane
-    V3 pn = v3(0, 0, 1);
-    if (hit) {
-        P = o + tbest * d;
-        const V3 lv = light - P;
-        ldist = gsqrt(dot(lv, lv));
-        Ld = normalize(lv);
-        const XPrim& px = v.XP[best];
-        pg = px.pad[0] < 254 ? px.pad[0] : 254;
-        pn = ld3(px.n);
-    }
+    const XHitFrame h = x_hit_frame(v, light, o, d, hit, best, tbest);
+    const V3 &P = h.P, &Ld = h.Ld;
     if (!no_shadow) {
         double tdummy;
-        int sb;
-        const int skip_s = (pg < 254 && fabs(dot(Ld, pn)) >= skip_cos) ? pg : 254;
-        if constexpr (FLAT) sb = wf_flat<true, TRI>(INFINITY, v.FT, sc.n_xflat, v.LH, P, Ld, ldist, hit, tdummy, nnode, nprim, st_steps, skip_s);
-        else if constexpr (LDS) sb = wf_trace<true, true, false, SH, TRI, false>(INFINITY, v.LW, v.LH, P, Ld, ldist, hit, v.nst, tdummy, nnode, nprim, st_steps, skip_s);
-        else if constexpr (CN) sb = wf_trace<true, false, false, SH, TRI, true>(INFINITY, sc.xcnodes, sc.xhot, P, Ld, ldist, hit, v.nst, tdummy, nnode, nprim, st_steps);
-        else sb = wf_trace<true, false, false, SH, TRI, true>(INFINITY, sc.xwnodes, sc.xhot, P, Ld, ldist, hit, v.nst, tdummy, nnode, nprim, st_steps, skip_s);
-        occl = sb >= 0;
+        const int skip_s = x_own_plane(h.pg, h.pn, Ld, skip_cos);
+        occl = x_query<true, LDS, SH, TRI, CN, FLAT>(sc, v, INFINITY, P, Ld, h.ldist, hit, tdummy, nnode, nprim, st_steps, skip_s) >= 0;
         if (STATS) wf_wave_steps(st_steps, ws.it_s, ws.ln_s);
     }
     if (STATS) {
@@ -574,7 +565,7 @@ __device__ __forceinline__ bool x_segment(const DevScene& sc, const WFView& v, c
         if (cont) {
             v.pl[0] = L.x; v.pl[256] = L.y; v.pl[512] = L.z;
             v.pl[768] = T.x; v.pl[1024] = T.y; v.pl[1280] = T.z;
-            if (splane) *splane = (pg < 254 && fabs(dot(d, pn)) >= skip_cos) ? pg : 254;
+            if (splane) *splane = x_own_plane(h.pg, h.pn, d, skip_cos);
         }
     }
     if (STATS) ws.cyc_sh += clock64() - c0;
@@ -598,7 +589,7 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
     if (*(volatile unsigned*)a.take >= n_in) return;   // nothing left (before staging the scene)
     extern __shared__ int4 lds_dyn[];
     const WFView v = wf_stage<LDS>(sc, lds_dyn);
-    const bool no_shadow = (xflags & 4) != 0;
+    const bool no_shadow = (xflags & XF_NO_SHADOW) != 0;
     const int lane = threadIdx.x & 63;
     uint32_t nnode = 0, nprim = 0, nrays = 0, nres = 0, npx = 0;
     const long long qc = qin.cap, oc = qout.cap;
@@ -658,7 +649,7 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
         }
         WFSegStats ws;
         // (the queue carries no plane: the closest ray is not skipped here, the shadow ray is)
-        const double skip_cos = sc.x_skip_a * fmax(fabs(cam.pos.x), fmax(fabs(cam.pos.y), fabs(cam.pos.z))) + sc.x_skip_b;
+        const double skip_cos = x_skip_cos(sc, cam.pos);
         const float far_r = ray_far_r(sc, cam.pos);   // (far cameras: gi_dev.h ray_org32)
         int splane = 254;
         const bool cont = x_segment<false, LDS, SH, TRI, CN, FLAT>(sc, v, light, depth, no_shadow, act, [&] { return PathId{key, smp, b}; }, o, d, L, T,
@@ -711,7 +702,7 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
     unsigned long long* stats, WFArgs a, int xflags) {
     extern __shared__ int4 lds_dyn[];
     const WFView v = wf_stage<LDS>(sc, lds_dyn);
-    const bool no_shadow = (xflags & 4) != 0;
+    const bool no_shadow = (xflags & XF_NO_SHADOW) != 0;
     const int lane = threadIdx.x & 63;
     const unsigned long long total = (unsigned long long)*a.n_list * (unsigned long long)a.ns;
     // run length: up to GI_SEG_TAKE batches of 64 units per atomic (background-heavy frames burn units
@@ -735,7 +726,7 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
     V3 o = cam.pos, d = v3(1, 0, 0), L = v3(0, 0, 0), T = v3(1, 1, 1);
     int splane = 254;   // the own-plane skip of the lane's next ray (254: none; primary rays)
     // (gi_build.cpp assign_plane_groups: the bound on |d . n| above which a surface's own plane is skipped)
-    const double skip_cos = sc.x_skip_a * fmax(fabs(cam.pos.x), fmax(fabs(cam.pos.y), fabs(cam.pos.z))) + sc.x_skip_b;
+    const double skip_cos = x_skip_cos(sc, cam.pos);
     const float far_r = ray_far_r(sc, cam.pos);   // (far cameras: gi_dev.h ray_org32)
     WFSegStats ws;
     const uint64_t t_begin = STATS ? clock64() : 0;
@@ -854,10 +845,10 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
 }
 
 // Known-answer hook (gi_kat_x_query; tests): the three queries of one path segment, one ray per
-// lane, with x_segment's calls and template arguments and k_seg's staging, so a test sees the
-// (t, primitive) answers themselves.  Record i: o, d, light, d2 (12 doubles).  The closest hit of
-// (o, d) without a skip; from its point P the any-hit query toward the light and the closest hit
-// of (P, d2), each with the own-plane skip by x_segment's rule.  Lanes past n run the queries
+// lane, through x_segment's own helpers (x_query, x_hit_frame, x_own_plane, x_skip_cos) and k_seg's
+// staging, so a test sees the (t, primitive) answers themselves.  Record i: o, d, light, d2 (12 doubles).
+// The closest hit of (o, d) without a skip; from its point P the any-hit query toward the light and the
+// closest hit of (P, d2), each with the own-plane skip.  Lanes past n run the queries
 // without a ray.  oi[5 i ..]: prim1, occl (-1 without a hit), skip_s, prim2, skip2; od[2 i ..]:
 // t1, t2; od[2 n]: the launch's skip_cos.
 template <bool LDS, bool W4, bool SH, bool TRI, bool CN, bool FLAT>
@@ -867,8 +858,7 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
     const WFView v = wf_stage<LDS>(sc, lds_dyn);
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     const bool act = i < (long long)n;
-    // (k_seg's expression)
-    const double skip_cos = sc.x_skip_a * fmax(fabs(cam_pos.x), fmax(fabs(cam_pos.y), fabs(cam_pos.z))) + sc.x_skip_b;
+    const double skip_cos = x_skip_cos(sc, cam_pos);
     const float far_r = ray_far_r(sc, cam_pos);   // (as k_seg: gi_dev.h ray_org32)
     V3 o = v3(0, 0, 0), d = v3(1, 0, 0), light = v3(0, 0, 0), d2 = v3(1, 0, 0);
     if (act) {
@@ -879,43 +869,19 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
         d2 = v3(q[9], q[10], q[11]);
     }
     uint32_t nnode = 0, nprim = 0, st_steps = 0;
-    // ---- closest hit (x_segment's calls, a primary ray: no skip)
+    // ---- closest hit (a primary ray: no skip)
     double t1 = INFINITY;
-    int p1;
-    if constexpr (FLAT) p1 = wf_flat<false, TRI>(far_r, v.FT, sc.n_xflat, v.LH, o, d, INFINITY, act, t1, nnode, nprim, st_steps, 254);
-    else if constexpr (LDS) p1 = wf_trace<false, true, false, SH, TRI, false>(far_r, v.LW, v.LH, o, d, INFINITY, act, v.nst, t1, nnode, nprim, st_steps, 254);
-    else if constexpr (CN) p1 = wf_trace<false, false, false, SH, TRI, true>(far_r, sc.xcnodes, sc.xhot, o, d, INFINITY, act, v.nst, t1, nnode, nprim, st_steps);
-    else p1 = wf_trace<false, false, false, SH, TRI, true>(far_r, sc.xwnodes, sc.xhot, o, d, INFINITY, act, v.nst, t1, nnode, nprim, st_steps, 254);
+    const int p1 = x_query<false, LDS, SH, TRI, CN, FLAT>(sc, v, far_r, o, d, INFINITY, act, t1, nnode, nprim, st_steps, 254);
     const bool hit = act && p1 >= 0;
-    V3 P = o, Ld = v3(0, 0, 1);
-    double ldist = 0.0;
-    int pg = 254;
-    V3 pn = v3(0, 0, 1);
-    if (hit) {
-        P = o + t1 * d;
-        const V3 lv = light - P;
-        ldist = gsqrt(dot(lv, lv));
-        Ld = normalize(lv);
-        const XPrim& px = v.XP[p1];
-        pg = px.pad[0] < 254 ? px.pad[0] : 254;
-        pn = ld3(px.n);
-    }
+    const XHitFrame h = x_hit_frame(v, light, o, d, hit, p1, t1);
     // ---- shadow any-hit
     double tdummy;
-    int sb;
-    const int skip_s = (pg < 254 && fabs(dot(Ld, pn)) >= skip_cos) ? pg : 254;
-    if constexpr (FLAT) sb = wf_flat<true, TRI>(INFINITY, v.FT, sc.n_xflat, v.LH, P, Ld, ldist, hit, tdummy, nnode, nprim, st_steps, skip_s);
-    else if constexpr (LDS) sb = wf_trace<true, true, false, SH, TRI, false>(INFINITY, v.LW, v.LH, P, Ld, ldist, hit, v.nst, tdummy, nnode, nprim, st_steps, skip_s);
-    else if constexpr (CN) sb = wf_trace<true, false, false, SH, TRI, true>(INFINITY, sc.xcnodes, sc.xhot, P, Ld, ldist, hit, v.nst, tdummy, nnode, nprim, st_steps);
-    else sb = wf_trace<true, false, false, SH, TRI, true>(INFINITY, sc.xwnodes, sc.xhot, P, Ld, ldist, hit, v.nst, tdummy, nnode, nprim, st_steps, skip_s);
+    const int skip_s = x_own_plane(h.pg, h.pn, h.Ld, skip_cos);
+    const int sb = x_query<true, LDS, SH, TRI, CN, FLAT>(sc, v, INFINITY, h.P, h.Ld, h.ldist, hit, tdummy, nnode, nprim, st_steps, skip_s);
     // ---- the next segment's closest hit, leaving the surface along d2
-    const int skip2 = (pg < 254 && fabs(dot(d2, pn)) >= skip_cos) ? pg : 254;
+    const int skip2 = x_own_plane(h.pg, h.pn, d2, skip_cos);
     double t2 = INFINITY;
-    int p2;
-    if constexpr (FLAT) p2 = wf_flat<false, TRI>(far_r, v.FT, sc.n_xflat, v.LH, P, d2, INFINITY, hit, t2, nnode, nprim, st_steps, skip2);
-    else if constexpr (LDS) p2 = wf_trace<false, true, false, SH, TRI, false>(far_r, v.LW, v.LH, P, d2, INFINITY, hit, v.nst, t2, nnode, nprim, st_steps, skip2);
-    else if constexpr (CN) p2 = wf_trace<false, false, false, SH, TRI, true>(far_r, sc.xcnodes, sc.xhot, P, d2, INFINITY, hit, v.nst, t2, nnode, nprim, st_steps);
-    else p2 = wf_trace<false, false, false, SH, TRI, true>(far_r, sc.xwnodes, sc.xhot, P, d2, INFINITY, hit, v.nst, t2, nnode, nprim, st_steps, skip2);
+    const int p2 = x_query<false, LDS, SH, TRI, CN, FLAT>(sc, v, far_r, h.P, d2, INFINITY, hit, t2, nnode, nprim, st_steps, skip2);
     if (act) {
         oi[5 * i] = p1 >= 0 ? p1 : -1;
         oi[5 * i + 1] = hit ? (sb >= 0 ? 1 : 0) : -1;
@@ -937,35 +903,30 @@ size_t wf_slot_bytes() { return kWfSlotBytes; }
 // there, 96 VGPRs and 120 B of scratch, 4.79 ms; profiles/r06_ab.txt)
 size_t wf_scene_lds_bytes(const DevScene& sc) { return (size_t)sc.x_lds_bytes + (GI_XFLAT_LDS ? (size_t)sc.n_xflat * sizeof(XFlatLeaf) : 0); }
 
-// The kernel variant for a scene: f(LDS, W4, SH, TRI, CN, FLAT) with each a std::integral_constant<bool>
-// (kv: 2 * LDS-resident + light-shading, XLaunchCfg::kv; flat: the flat leaf query, LDS-resident scenes
-// whose table applies -- DevScene::x_flat -- unless GI_X_FLAT=0)
+// The kernel variant for a scene: f(XTag) (var: XLaunchCfg::var; flat: the flat leaf query, LDS-resident
+// scenes whose table applies -- DevScene::x_flat -- unless GI_X_FLAT=0).  TRI of an LDS-resident scene is
+// its W4 (light shading); HBM-resident scenes run SH = false.
 template <typename F>
-void wf_dispatch(const DevScene& sc, int kv, bool flat, F&& f) {
-    using B = std::true_type;
-    using N = std::false_type;
-    const bool lds = kv >= 2, w4 = kv == 3, sh = sc.x_max_depth <= 7, tr = sc.x_tri_only != 0;
-    const bool cn = !lds && sc.xcnodes != nullptr;
-    if (lds && flat && sc.x_flat) {   // (SH only shapes the tree walk's level masks: one flat kernel per W4)
-        if (w4) f(B{}, B{}, B{}, B{}, N{}, B{}); else f(B{}, N{}, B{}, N{}, N{}, B{});
-    } else if (lds) {
-        if (w4) { if (sh) f(B{}, B{}, B{}, B{}, N{}, N{}); else f(B{}, B{}, N{}, B{}, N{}, N{}); }
-        else { if (sh) f(B{}, N{}, B{}, N{}, N{}, N{}); else f(B{}, N{}, N{}, N{}, N{}, N{}); }
-    } else if (cn) {
-        if (tr) f(N{}, N{}, N{}, B{}, B{}, N{}); else f(N{}, N{}, N{}, N{}, B{}, N{});
-    } else {
-        if (tr) f(N{}, N{}, N{}, B{}, N{}, N{}); else f(N{}, N{}, N{}, N{}, N{}, N{});
-    }
+void wf_dispatch(const DevScene& sc, XVariant var, bool flat, bool stats, F&& f) {
+    if (var.lds && flat && sc.x_flat)   // (SH only shapes the tree walk's level masks: one flat kernel per W4)
+        with_bools([&](auto S, auto W) { f(XTag<S.value, true, W.value, false, true, W.value, false, true>{}); }, stats, var.w4);
+    else if (var.lds)
+        with_bools([&](auto S, auto W, auto H) { f(XTag<S.value, true, W.value, false, H.value, W.value, false, false>{}); },
+                   stats, var.w4, sc.x_max_depth <= 7);
+    else
+        with_bools([&](auto S, auto T, auto C) { f(XTag<S.value, false, false, false, false, T.value, C.value, false>{}); },
+                   stats, sc.x_tri_only != 0, sc.xcnodes != nullptr);
 }
+template <typename V>
+constexpr auto seg_kernel(V) { return &k_seg<V::stats, V::lds, V::w4, V::sh, V::tri, V::cn, V::flat>; }
+template <typename V>
+constexpr auto bounce_kernel(V) { return &k_wf_bounce<V::stats, V::lds, V::w4, V::sh, V::tri, V::cn, V::flat>; }
 
 // resident workgroups per CU of the kernel a form (1: k_wf_bounce, 2: k_seg) runs for this scene
-hipError_t wf_occupancy(const DevScene& sc, int kv, bool flat, size_t lds_bytes, int form, int* per_cu) {
+hipError_t wf_occupancy(const DevScene& sc, XVariant var, bool flat, size_t lds_bytes, int form, int* per_cu) {
     hipError_t e = hipSuccess;
-    wf_dispatch(sc, kv, flat, [&](auto L, auto W, auto SHt, auto T, auto C, auto FL) {
-        constexpr bool l = decltype(L)::value, w = decltype(W)::value, sh = decltype(SHt)::value,
-                       t = decltype(T)::value, c = decltype(C)::value, fl = decltype(FL)::value;
-        const void* f = form == 2 ? reinterpret_cast<const void*>(k_seg<false, l, w, sh, t, c, fl>)
-                                  : reinterpret_cast<const void*>(k_wf_bounce<false, l, w, sh, t, c, fl>);
+    wf_dispatch(sc, var, flat, false, [&](auto V) {
+        const void* f = form == 2 ? reinterpret_cast<const void*>(seg_kernel(V)) : reinterpret_cast<const void*>(bounce_kernel(V));
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, f, 256, lds_bytes);
     });
     return e;
@@ -976,7 +937,7 @@ hipError_t wf_occupancy(const DevScene& sc, int kv, bool flat, size_t lds_bytes,
 //    slot, those past the work list's end return at once on the device) `depth` bounce launches;
 //    counters: 2 per bounce (take, n_out), zeroed per chunk.
 //  form 2 (segment-synchronous): one persistent launch; counter: a 64-bit unit count at xs.wcnt.
-hipError_t launch_wf(const DevScene& sc, int kv, size_t lds_bytes, int resident, int form, const CamDev& cam, V3 light,
+hipError_t launch_wf(const DevScene& sc, XVariant var, size_t lds_bytes, int resident, int form, const CamDev& cam, V3 light,
                      int w, int h, int y0, const gi_opts& o, double* rgb, uint8_t* rgb8, const XScratch& xs,
                      const unsigned* n_list_dev, unsigned long long* stats, int xflags, hipStream_t stream,
                      hipEvent_t ev_begin, hipEvent_t ev_end) {
@@ -985,7 +946,7 @@ hipError_t launch_wf(const DevScene& sc, int kv, size_t lds_bytes, int resident,
     const int s0 = o.sample_end > 0 ? o.sample_begin : 0, s1 = o.sample_end > 0 ? o.sample_end : o.spp;
     const dim3 grid((unsigned)std::max(1, resident)), block(256);
     hipError_t e = hipSuccess;
-    const bool flat = (xflags & 64) == 0;   // (bit 6: GI_X_FLAT=0)
+    const bool flat = (xflags & XF_NO_FLAT) == 0;   // (GI_X_FLAT=0)
     if (form == 2) {   // (the unit counter xs.wcnt[0..1] was zeroed by k_x_classify)
         WFArgs a{};
         a.list = xs.list;
@@ -995,11 +956,8 @@ hipError_t launch_wf(const DevScene& sc, int kv, size_t lds_bytes, int resident,
         a.s0 = (unsigned)s0;
         a.ns = (unsigned)(s1 - s0);
         if (ev_begin) (void)hipEventRecord(ev_begin, stream);
-        wf_dispatch(sc, kv, flat, [&](auto L, auto W, auto SHt, auto T, auto C, auto FL) {
-            constexpr bool l = decltype(L)::value, wv = decltype(W)::value, sh = decltype(SHt)::value,
-                           t = decltype(T)::value, c = decltype(C)::value, fl = decltype(FL)::value;
-            if (stats) hipLaunchKernelGGL((k_seg<true, l, wv, sh, t, c, fl>), grid, block, lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, rgb, rgb8, stats, a, xflags);
-            else hipLaunchKernelGGL((k_seg<false, l, wv, sh, t, c, fl>), grid, block, lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, rgb, rgb8, stats, a, xflags);
+        wf_dispatch(sc, var, flat, stats != nullptr, [&](auto V) {
+            hipLaunchKernelGGL(seg_kernel(V), grid, block, lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, rgb, rgb8, stats, a, xflags);
         });
         if (ev_end) (void)hipEventRecord(ev_end, stream);
         return hipGetLastError();
@@ -1031,11 +989,8 @@ hipError_t launch_wf(const DevScene& sc, int kv, size_t lds_bytes, int resident,
             qin.id = reinterpret_cast<uint2*>(xs.wid[(b + 1) & 1]);
             qout.r = xs.wq[b & 1];
             qout.id = reinterpret_cast<uint2*>(xs.wid[b & 1]);
-            wf_dispatch(sc, kv, flat, [&](auto L, auto W, auto SHt, auto T, auto C, auto FL) {
-                constexpr bool l = decltype(L)::value, wv = decltype(W)::value, sh = decltype(SHt)::value,
-                               t = decltype(T)::value, c = decltype(C)::value, fl = decltype(FL)::value;
-                if (stats) hipLaunchKernelGGL((k_wf_bounce<true, l, wv, sh, t, c, fl>), grid, block, lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, b, rgb, rgb8, stats, a, qin, qout, xflags);
-                else hipLaunchKernelGGL((k_wf_bounce<false, l, wv, sh, t, c, fl>), grid, block, lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, b, rgb, rgb8, stats, a, qin, qout, xflags);
+            wf_dispatch(sc, var, flat, stats != nullptr, [&](auto V) {
+                hipLaunchKernelGGL(bounce_kernel(V), grid, block, lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, b, rgb, rgb8, stats, a, qin, qout, xflags);
             });
         }
     }
@@ -1044,23 +999,21 @@ hipError_t launch_wf(const DevScene& sc, int kv, size_t lds_bytes, int resident,
 }
 
 // gi_kat_x_query's launch: k_seg's variant for the scene (wf_dispatch), one ray per lane
-hipError_t launch_x_query_kat(const DevScene& sc, int kv, bool flat, size_t lds_bytes, V3 cam_pos, int n,
+hipError_t launch_x_query_kat(const DevScene& sc, XVariant var, bool flat, size_t lds_bytes, V3 cam_pos, int n,
                               const double* recs, int32_t* oi, double* od, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
     const dim3 grid((unsigned)(((long long)n + 255) / 256)), block(256);
-    wf_dispatch(sc, kv, flat, [&](auto L, auto W, auto SHt, auto T, auto C, auto FL) {
-        constexpr bool l = decltype(L)::value, wv = decltype(W)::value, sh = decltype(SHt)::value,
-                       t = decltype(T)::value, c = decltype(C)::value, fl = decltype(FL)::value;
-        hipLaunchKernelGGL((k_x_query_kat<l, wv, sh, t, c, fl>), grid, block, lds_bytes, stream, sc, cam_pos, n, recs, oi, od);
+    wf_dispatch(sc, var, flat, false, [&](auto V) {
+        using T = decltype(V);
+        hipLaunchKernelGGL((k_x_query_kat<T::lds, T::w4, T::sh, T::tri, T::cn, T::flat>), grid, block, lds_bytes, stream, sc, cam_pos, n, recs, oi, od);
     });
     return hipGetLastError();
 }
 
 // the variant (LDS, W4, SH, TRI, CN, FLAT) wf_dispatch picks for a scene: what gi_kat_x_variant reports
-void wf_variant(const DevScene& sc, int kv, bool flat, int32_t out[6]) {
-    wf_dispatch(sc, kv, flat, [&](auto L, auto W, auto SHt, auto T, auto C, auto FL) {
-        out[0] = decltype(L)::value; out[1] = decltype(W)::value; out[2] = decltype(SHt)::value;
-        out[3] = decltype(T)::value; out[4] = decltype(C)::value; out[5] = decltype(FL)::value;
+void wf_variant(const DevScene& sc, XVariant var, bool flat, int32_t out[6]) {
+    wf_dispatch(sc, var, flat, false, [&](auto V) {
+        out[0] = V.lds; out[1] = V.w4; out[2] = V.sh; out[3] = V.tri; out[4] = V.cn; out[5] = V.flat;
     });
 }
 

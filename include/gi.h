@@ -328,7 +328,8 @@ int gi_kat_expbox(int n, const double* recs, int32_t* out);
 /* Known-answer hook (a TEST hook; ABI 11): the Mode X device queries ray by ray.  n host records of
  * 12 doubles -- o[3], d[3], light[3], d2[3]; d and d2 are used as given -- each run as one path
  * segment's three queries by the kernel variant the segment form (k_seg) runs for this scene, the
- * scene staged as k_seg stages it:
+ * scene staged as k_seg stages it, through the functions a k_seg segment itself calls for its queries,
+ * its hit frame and its own-plane skip rule (not a copy of them):
  *   prim1, t1 : the closest hit of the ray (o, d): primitive index (entities in push order, an
  *               ExpQuad as its 2 triangles) and distance; -1 and +inf without a hit;
  *   occl      : from the hit point P = o + t1 d, 1 / 0 whether anything lies between P and `light`
