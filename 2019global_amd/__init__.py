@@ -36,7 +36,7 @@ __all__ = [
     "GIError", "lib", "Camera", "Material", "Octree", "ImpSphere", "ImpTriangle", "ExpQuad",
     "ExpSphere", "ExpCube", "ExpCone", "ExpRectangle", "ExpBox",
     "RayTracer", "DeviceScene", "MODE_R", "MODE_X", "STAT_RAYS", "STAT_NODES", "STAT_PRIMS",
-    "STAT_PIXELS", "TILE", "MultiScene", "devices_from_env", "obj_entities",
+    "STAT_PIXELS", "TILE", "MultiScene", "devices_from_env", "obj_entities", "RAY_DOUBLES",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -62,7 +62,8 @@ STAT_X_IT_RS, STAT_X_LN_RS, STAT_X_IT_ST, STAT_X_LN_ST = 20, 21, 22, 23
 STAT_R_PAIRS, STAT_R_OVF_TILES = 24, 25
 STATS_N = 26
 TILE = 8
-ABI_VERSION = 11
+ABI_VERSION = 12
+RAY_DOUBLES = 8   # a ray record of the batched queries: o[3], d[3], tmax, reserved (gi.h GI_RAY_DOUBLES)
 
 
 class GIError(RuntimeError):
@@ -112,7 +113,8 @@ EXPORTS = ["gi_abi_version", "gi_last_error", "gi_camera_init", "gi_scene_create
            "gi_scene_get_info", "gi_render", "gi_render_device", "gi_shard_tiles", "gi_unshard_device",
            "gi_trace_ray", "gi_kat_expbox", "gi_kat_x_query", "gi_kat_x_variant", "gi_scene_kernel_ms", "gi_scene_x_form", "gi_scene_r_kernel", "gi_octree_create", "gi_octree_destroy",
            "gi_octree_intersect", "gi_multi_create", "gi_multi_destroy", "gi_multi_info", "gi_multi_render", "gi_device_count",
-           "gi_device_list", "gi_build_id", "gi_obj_parse"]
+           "gi_device_list", "gi_build_id", "gi_obj_parse", "gi_intersect", "gi_occluded", "gi_intersect_device",
+           "gi_occluded_device"]
 
 _lib = None
 _lock = threading.Lock()
@@ -151,6 +153,11 @@ def lib():
         ip = ctypes.POINTER(ctypes.c_int32)
         L.gi_kat_x_query.argtypes = [vp, i32, dp, dp, i32, ip, dp, ip, ip, ip, dp, ip, dp]
         L.gi_kat_x_variant.argtypes = [vp, i32, ip]
+        i64 = ctypes.c_int64
+        L.gi_intersect.argtypes = [vp, i64, dp, dp, ip, ip, dp]
+        L.gi_occluded.argtypes = [vp, i64, dp, ip]
+        L.gi_intersect_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
+        L.gi_occluded_device.argtypes = [vp, i64, vp, vp, vp]
         L.gi_scene_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)]
         L.gi_scene_x_form.argtypes = [vp, ctypes.POINTER(Opts), ctypes.POINTER(ctypes.c_int32)]
         L.gi_scene_r_kernel.argtypes = [vp, ctypes.POINTER(Opts), ctypes.POINTER(ctypes.c_int32)]
@@ -184,6 +191,15 @@ def build_id() -> str:
 def _check(rc: int, what: str) -> None:
     if rc != 0:
         raise GIError(f"{what} failed ({rc}): {lib().gi_last_error().decode()}")
+
+
+def _check_rays(rays) -> int:
+    """The ray count of a host ray array for DeviceScene.intersect / occluded; ValueError unless it is a
+    C-contiguous float64 array of shape (n, RAY_DOUBLES).  Checked before the library is touched."""
+    if not isinstance(rays, np.ndarray) or rays.dtype != np.float64 or rays.ndim != 2 or rays.shape[1] != RAY_DOUBLES or \
+            not rays.flags.c_contiguous:
+        raise ValueError(f"rays: a C-contiguous float64 array of shape (n, {RAY_DOUBLES}) -- o[3], d[3], tmax, reserved")
+    return int(rays.shape[0])
 
 
 def _d3(v) -> ctypes.Array:
@@ -525,6 +541,49 @@ class DeviceScene:
         _check(lib().gi_trace_ray(self._h, _d3(origin), _d3(direction), _d3(light), ctypes.byref(hit), rgb),
                "gi_trace_ray")
         return hit, tuple(rgb)
+
+    # ---- batched ray queries (gi.h "batched ray queries") ------------------------------------------
+    INTERSECT_OUTPUTS = ("t", "prim", "entity", "normal")
+
+    def intersect(self, rays: np.ndarray, want=INTERSECT_OUTPUTS) -> dict:
+        """Closest hits of host rays (gi_intersect): rays is a C-contiguous float64 array of shape
+        (n, RAY_DOUBLES) -- o[3], d[3] (used as given), tmax (may be inf), reserved.  Returns the
+        outputs named in want: "t" (n,) float64, "prim" and "entity" (n,) int32, "normal" (n, 3)
+        float64; a miss is t = inf, prim = entity = -1, normal = 0.  ValueError for any other input."""
+        n = _check_rays(rays)
+        want = tuple(want)
+        if not want or any(k not in self.INTERSECT_OUTPUTS for k in want) or len(set(want)) != len(want):
+            raise ValueError(f"intersect: want is a non-empty selection of {self.INTERSECT_OUTPUTS}")
+        m = max(n, 1)   # (a zero-length call still hands the library valid pointers)
+        bufs = {"t": np.empty(m, np.float64), "prim": np.empty(m, np.int32), "entity": np.empty(m, np.int32),
+                "normal": np.empty((m, 3), np.float64)}
+        ip, dp = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)
+        ptr = {k: (bufs[k].ctypes.data_as(dp if bufs[k].dtype == np.float64 else ip) if k in want else None)
+               for k in self.INTERSECT_OUTPUTS}
+        _check(lib().gi_intersect(self._h, n, rays.ctypes.data_as(dp), ptr["t"], ptr["prim"], ptr["entity"], ptr["normal"]),
+               "gi_intersect")
+        return {k: bufs[k][:n] for k in want}
+
+    def occluded(self, rays: np.ndarray) -> np.ndarray:
+        """Any hit of host rays (gi_occluded; rays as for intersect): (n,) int32, 1 where some primitive
+        lies at t in (1e-7, tmax), else 0."""
+        n = _check_rays(rays)
+        out = np.empty(max(n, 1), np.int32)
+        _check(lib().gi_occluded(self._h, n, rays.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                 out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), "gi_occluded")
+        return out[:n]
+
+    def intersect_device(self, n: int, d_rays: int, d_t: int = 0, d_prim: int = 0, d_entity: int = 0, d_normal: int = 0,
+                         stream: int = 0) -> None:
+        """Asynchronous closest hits of n device-resident rays into device buffers (gi_intersect_device);
+        pointers are ints, an output of 0 is not written."""
+        _check(lib().gi_intersect_device(self._h, int(n), d_rays or None, d_t or None, d_prim or None, d_entity or None,
+                                         d_normal or None, stream or None), "gi_intersect_device")
+
+    def occluded_device(self, n: int, d_rays: int, d_occluded: int, stream: int = 0) -> None:
+        """Asynchronous any-hit answers (int32, 1 / 0) of n device-resident rays (gi_occluded_device)."""
+        _check(lib().gi_occluded_device(self._h, int(n), d_rays or None, d_occluded or None, stream or None),
+               "gi_occluded_device")
 
     def kat_x_variant(self, flags: int = 0) -> dict:
         """The kernel variant kat_x_query runs with these flags (flags 0: k_seg's for this scene):

@@ -40,6 +40,7 @@ hipError_t launch_box_kat(int n, const double* recs, int32_t* out, hipStream_t s
 hipError_t launch_x_query(const DevScene& sc, const XLaunchCfg& xc, V3 cam_pos, int flags, int n, const double* recs,
                           int32_t* oi, double* od, hipStream_t stream);
 void x_query_variant(const DevScene& sc, const XLaunchCfg& xc, int flags, int32_t out[6]);
+hipError_t launch_ray_query(const DevScene& sc, const XLaunchCfg& xc, bool any, const CastIO& io, hipStream_t stream);
 }  // namespace gi
 
 using namespace gi;
@@ -821,6 +822,109 @@ int gi_trace_ray(gi_scene* s, const double origin[3], const double dir[3], const
         hit->v = hi[2];
         for (int k = 0; k < 3; ++k) { hit->point[k] = hd[k]; hit->normal[k] = hd[3 + k]; rgb[k] = hd[6 + k]; }
         return GI_OK;
+    });
+}
+
+// ---- batched ray queries (gi.h "batched ray queries"; gi_wf.hip k_cast) ------------------------
+// The scene's immutable records and launch configuration only: no lock, no ordering against the
+// scene's renders, nothing of the progressive-frame state (prog_key, prog_next, last) is touched.
+namespace {
+int check_ray_args(const gi_scene* s, int64_t n, const double* rays) {
+    if (!s) return fail(GI_ERR_ARG, "null scene");
+    if (n < 0) return fail(GI_ERR_ARG, "negative ray count");
+    if (n > 0 && !rays) return fail(GI_ERR_ARG, "null rays");
+    return GI_OK;
+}
+int ray_query_device(gi_scene* s, bool any, const CastIO& io, hipStream_t stream) {
+    if (reinterpret_cast<uintptr_t>(io.rays) & 15) return fail(GI_ERR_ARG, "device ray records must be 16-byte aligned");
+    int rc = bind_device(s->device);
+    if (rc) return rc;
+    const hipError_t e = launch_ray_query(s->dev, s->xcfg, any, io, stream);
+    return e == hipSuccess ? GI_OK : hip_fail(e, any ? "gi_occluded launch" : "gi_intersect launch");
+}
+// device staging of a host call: freed on scope exit
+struct DevBuf {
+    void* p = nullptr;
+    ~DevBuf() { (void)hipFree(p); }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
+};
+}  // namespace
+
+int gi_intersect_device(gi_scene* s, int64_t n, const double* d_rays, double* d_t, int32_t* d_prim, int32_t* d_entity,
+                        double* d_normal, void* stream) {
+    return guard([&]() -> int {
+        DeviceRestore keep;   // the caller's current device, restored on return
+        int rc = check_ray_args(s, n, d_rays);
+        if (rc) return rc;
+        if (!d_t && !d_prim && !d_entity && !d_normal) return fail(GI_ERR_ARG, "gi_intersect: every output is null");
+        if (n == 0) return GI_OK;
+        return ray_query_device(s, false, CastIO{d_rays, (long long)n, d_t, d_prim, d_entity, d_normal, nullptr},
+                                static_cast<hipStream_t>(stream));
+    });
+}
+
+int gi_occluded_device(gi_scene* s, int64_t n, const double* d_rays, int32_t* d_occluded, void* stream) {
+    return guard([&]() -> int {
+        DeviceRestore keep;   // the caller's current device, restored on return
+        int rc = check_ray_args(s, n, d_rays);
+        if (rc) return rc;
+        if (!d_occluded) return fail(GI_ERR_ARG, "gi_occluded: null output");
+        if (n == 0) return GI_OK;
+        return ray_query_device(s, true, CastIO{d_rays, (long long)n, nullptr, nullptr, nullptr, nullptr, d_occluded},
+                                static_cast<hipStream_t>(stream));
+    });
+}
+
+int gi_intersect(gi_scene* s, int64_t n, const double* rays, double* t, int32_t* prim, int32_t* entity, double* normal) {
+    return guard([&]() -> int {
+        DeviceRestore keep;   // the caller's current device, restored on return
+        int rc = check_ray_args(s, n, rays);
+        if (rc) return rc;
+        if (!t && !prim && !entity && !normal) return fail(GI_ERR_ARG, "gi_intersect: every output is null");
+        if (n == 0) return GI_OK;
+        if ((rc = bind_device(s->device))) return rc;
+        const size_t m = (size_t)n;
+        DevBuf dr, dt, dp, de, dn;
+        hipError_t e = dr.alloc(m * GI_RAY_DOUBLES * sizeof(double));
+        if (e == hipSuccess && t) e = dt.alloc(m * sizeof(double));
+        if (e == hipSuccess && prim) e = dp.alloc(m * sizeof(int32_t));
+        if (e == hipSuccess && entity) e = de.alloc(m * sizeof(int32_t));
+        if (e == hipSuccess && normal) e = dn.alloc(m * 3 * sizeof(double));
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc (ray query staging)");
+        if ((e = hipMemcpy(dr.p, rays, m * GI_RAY_DOUBLES * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess)
+            return hip_fail(e, "gi_intersect");
+        rc = ray_query_device(s, false, CastIO{static_cast<const double*>(dr.p), (long long)n, static_cast<double*>(dt.p),
+                                               static_cast<int32_t*>(dp.p), static_cast<int32_t*>(de.p),
+                                               static_cast<double*>(dn.p), nullptr}, nullptr);
+        if (rc) return rc;
+        if (t) e = hipMemcpy(t, dt.p, m * sizeof(double), hipMemcpyDeviceToHost);   // (synchronous copies on the launch's stream)
+        if (e == hipSuccess && prim) e = hipMemcpy(prim, dp.p, m * sizeof(int32_t), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && entity) e = hipMemcpy(entity, de.p, m * sizeof(int32_t), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && normal) e = hipMemcpy(normal, dn.p, m * 3 * sizeof(double), hipMemcpyDeviceToHost);
+        return e == hipSuccess ? GI_OK : hip_fail(e, "gi_intersect");
+    });
+}
+
+int gi_occluded(gi_scene* s, int64_t n, const double* rays, int32_t* occluded) {
+    return guard([&]() -> int {
+        DeviceRestore keep;   // the caller's current device, restored on return
+        int rc = check_ray_args(s, n, rays);
+        if (rc) return rc;
+        if (!occluded) return fail(GI_ERR_ARG, "gi_occluded: null output");
+        if (n == 0) return GI_OK;
+        if ((rc = bind_device(s->device))) return rc;
+        const size_t m = (size_t)n;
+        DevBuf dr, dc;
+        hipError_t e = dr.alloc(m * GI_RAY_DOUBLES * sizeof(double));
+        if (e == hipSuccess) e = dc.alloc(m * sizeof(int32_t));
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc (ray query staging)");
+        if ((e = hipMemcpy(dr.p, rays, m * GI_RAY_DOUBLES * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess)
+            return hip_fail(e, "gi_occluded");
+        rc = ray_query_device(s, true, CastIO{static_cast<const double*>(dr.p), (long long)n, nullptr, nullptr, nullptr, nullptr,
+                                              static_cast<int32_t*>(dc.p)}, nullptr);
+        if (rc) return rc;
+        e = hipMemcpy(occluded, dc.p, m * sizeof(int32_t), hipMemcpyDeviceToHost);
+        return e == hipSuccess ? GI_OK : hip_fail(e, "gi_occluded");
     });
 }
 

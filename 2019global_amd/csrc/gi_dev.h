@@ -201,7 +201,10 @@ __device__ __forceinline__ F3 inv_dir(V3 d) {
 // tests keep the ray as given, so every (t, primitive) is unchanged.
 __device__ __forceinline__ F3 ray_org32(V3 o, V3 d, float far_r) {
     F3 of = f3((float)o.x, (float)o.y, (float)o.z);
-    if (far_r < INFINITY) {   // uniform over the launch (ray_far_r): a scalar branch, not taken for near cameras
+    // far_r is uniform over the launch: a scalar branch, not taken for near cameras (ray_far_r).  The ray
+    // queries (gi_wf.hip k_cast) pass the scene's x_far_r always -- their origins are the caller's -- and
+    // take the choice below per lane
+    if (far_r < INFINITY) {
         if (fmax(fabs(o.x), fmax(fabs(o.y), fabs(o.z))) > (double)far_r) {
             const double dd = dot(d, d);
             const double t0 = -dot(o, d) / dd - 0.25 * (double)far_r / gsqrt(dd);

@@ -2383,6 +2383,12 @@ hipError_t x_launch_config(const DevScene& sc, int device, XLaunchCfg& cfg) {
     e = wf_occupancy(sc, cfg.var, flat, cfg.wf_lds_bytes, 2, &per_cu);
     if (e != hipSuccess) return e;
     cfg.seg_resident = std::max(1, cus) * std::max(1, per_cu);
+    e = wf_occupancy(sc, cfg.var, flat, cfg.wf_lds_bytes, 3, &per_cu);   // the ray queries (k_cast)
+    if (e != hipSuccess) return e;
+    cfg.cast_resident = std::max(1, cus) * std::max(1, per_cu);
+    e = wf_occupancy(sc, cfg.var, flat, cfg.wf_lds_bytes, 4, &per_cu);
+    if (e != hipSuccess) return e;
+    cfg.occl_resident = std::max(1, cus) * std::max(1, per_cu);
     return hipSuccess;
 }
 
@@ -2549,6 +2555,15 @@ hipError_t launch_x_query(const DevScene& sc, const XLaunchCfg& xc, V3 cam_pos, 
 void x_query_variant(const DevScene& sc, const XLaunchCfg& xc, int flags, int32_t out[6]) {
     const XQueryCfg c = x_query_cfg(xc, flags);
     wf_variant(sc, c.var, c.flat, out);
+}
+
+// gi_intersect* / gi_occluded*: k_cast in the variant, the flat choice and the dynamic LDS of a k_seg
+// launch on this scene -- what gi_kat_x_variant(scene, 0, ...) reports
+hipError_t launch_cast(const DevScene& sc, XVariant var, bool flat, size_t lds_bytes, int resident, bool any, const CastIO& io,
+                       hipStream_t stream);
+hipError_t launch_ray_query(const DevScene& sc, const XLaunchCfg& xc, bool any, const CastIO& io, hipStream_t stream) {
+    const XQueryCfg c = x_query_cfg(xc, 0);
+    return launch_cast(sc, c.var, c.flat, c.lds_bytes, any ? xc.occl_resident : xc.cast_resident, any, io, stream);
 }
 
 hipError_t launch_trace_ray(const DevScene& sc, V3 o, V3 d, V3 light, int32_t* out_i, double* out_d, hipStream_t stream) {

@@ -342,6 +342,19 @@ struct XLaunchCfg {
     size_t wf_lds_bytes = 0; // wavefront Mode X (k_wf_bounce, k_seg): dynamic LDS per workgroup
     int wf_resident = 1;     //   and the resident workgroups of k_wf_bounce
     int seg_resident = 1;    //   and of k_seg
+    int cast_resident = 1;   // the ray queries (k_cast, gi_wf.hip): closest hit
+    int occl_resident = 1;   //   and any hit
+};
+
+// One call of the public ray queries (gi_intersect*, gi_occluded*; gi_wf.hip k_cast): device pointers.
+struct CastIO {
+    const double* rays;   // n records of 8 doubles (o[3], d[3], tmax, reserved), 16-byte aligned
+    long long n;
+    double* t;            // closest hit: distance, primitive, entity, facing unit normal (3 per ray);
+    int32_t* prim;        //   a null pointer: that output is not written
+    int32_t* ent;
+    double* nrm;
+    int32_t* occl;        // any hit: 1 / 0
 };
 
 }  // namespace gi

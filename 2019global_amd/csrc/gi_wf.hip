@@ -894,6 +894,86 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
     if (i == 0) od[2 * (long long)n] = skip_cos;
 }
 
+// The public ray queries (gi_intersect*, gi_occluded*; DESIGN.md §5 "Ray queries"): the closest hit
+// (ANY = false: the (t, primitive) minimum over t in (MX_TMIN, tmax), with the primitive's entity and
+// the facing unit normal) or any hit (ANY: 1 / 0) of n caller-supplied rays, through x_query in the
+// variant a k_seg launch on the scene runs, the scene staged once per workgroup as k_seg stages it.
+// Persistent grid, static schedule: wave w of the launch's W waves takes the batches of 64 rays
+// w, w + W, ... -- no device counter, so concurrent calls share nothing, and nothing of the scene's
+// render scratch (work list, counters, per-sample rows) is read or written.
+//  skip: none (254).  A caller's ray leaves no known surface, so no plane group may be left out.
+//  far_r: the scene's x_far_r always.  Origins are the caller's, so the choice in ray_org32 between
+//    the origin and a point of the ray near the scene is made per lane here (divergent where a wave
+//    mixes near and far origins) instead of once per launch.  With a finite tmax the rule stays
+//    conservative for the reason it is with the best t: a far ray's box distances count from the
+//    shifted point o + t0 d (t0 > 0) while tmax, like the best t it initialises in wf_trace and
+//    wf_flat (tb, tbf, phase A's tfa), counts from o.  A box that begins at s from the shifted point
+//    begins at s + t0 from o, so the exact bound from the shifted point would be tmax - t0; testing
+//    s against tmax itself only keeps more boxes, and wf_flat's early exit (tn2 > tbf) drops its
+//    other candidates only when they begin beyond tmax + t0.  The fp64 primitive tests take o, d and
+//    tmax as given, and compare t < tmax strictly (a first hit at t == tmax finds best = -1, which
+//    no primitive index is below): the interval is open at both ends.
+//  Malformed rays (a non-finite component of o or d, a zero d, a NaN tmax) and rays whose tmax is
+//    not above MX_TMIN run as lanes without a ray, on a harmless stand-in ray: a miss, and no NaN
+//    reaches a comparison that other lanes' control flow shares.
+// Resources (hipcc -S, gfx950): DESIGN.md §9 "Ray queries".
+template <bool ANY, bool LDS, bool W4, bool SH, bool TRI, bool CN, bool FLAT>
+__global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_WAVES) void k_cast(DevScene sc, CastIO io) {
+    extern __shared__ int4 lds_dyn[];
+    const WFView v = wf_stage<LDS>(sc, lds_dyn);
+    const int lane = threadIdx.x & 63;
+    const long long stride = 64ll * (long long)gridDim.x * (long long)(blockDim.x >> 6);
+    for (long long base = 64ll * ((long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)); base < io.n; base += stride) {
+        const long long i = base + lane;
+        const bool in = i < io.n;
+        V3 o = v3(0, 0, 0), d = v3(1, 0, 0);
+        double tmax = INFINITY;
+        bool act = false;
+        if (in) {   // the 64-byte record in four 16-byte loads
+            const double2* q = reinterpret_cast<const double2*>(io.rays) + 4 * i;
+            const double2 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
+            const V3 ro = v3(q0.x, q0.y, q1.x), rd = v3(q1.y, q2.x, q2.y);
+            const bool fin = __builtin_isfinite(ro.x) & __builtin_isfinite(ro.y) & __builtin_isfinite(ro.z) &
+                             __builtin_isfinite(rd.x) & __builtin_isfinite(rd.y) & __builtin_isfinite(rd.z);
+            const bool nz = (rd.x != 0.0) | (rd.y != 0.0) | (rd.z != 0.0);
+            act = fin & nz & (q3.x > MX_TMIN);   // (false for a NaN tmax; q3.y is reserved)
+            if (act) {
+                o = ro;
+                d = rd;
+                tmax = q3.x;
+            }
+        }
+        uint32_t nnode = 0, nprim = 0, nsteps = 0;
+        double tb = INFINITY;
+        const int best = x_query<ANY, LDS, SH, TRI, CN, FLAT>(sc, v, sc.x_far_r, o, d, tmax, act, tb, nnode, nprim, nsteps, 254);
+        const bool hit = act && best >= 0;
+        if constexpr (ANY) {
+            if (in) io.occl[i] = hit ? 1 : 0;
+        } else {
+            if (in) {
+                if (io.t) io.t[i] = hit ? tb : INFINITY;
+                if (io.prim) io.prim[i] = hit ? best : -1;
+                if (io.ent || io.nrm) {
+                    int ent = -1;
+                    V3 N = v3(0, 0, 0);
+                    if (hit) {   // x_segment's facing normal
+                        const XPrim& p = v.XP[best];
+                        ent = p.ent;
+                        const V3 P = o + tb * d;
+                        N = (TRI || p.kind == 0) ? ld3(p.n) : normalize(P - ld3(p.a));
+                        N = dot(d, N) < 0 ? N : -N;
+                    }
+                    if (io.ent) io.ent[i] = ent;
+                    if (io.nrm) {
+                        double* q = io.nrm + 3 * i;
+                        q[0] = N.x; q[1] = N.y; q[2] = N.z;
+                    }
+                }
+            }
+        }
+    }
+}
+
 }  // namespace
 
 // dynamic LDS of the bounce kernel beyond the scene / level stack: the per-lane path slots
@@ -922,11 +1002,18 @@ constexpr auto seg_kernel(V) { return &k_seg<V::stats, V::lds, V::w4, V::sh, V::
 template <typename V>
 constexpr auto bounce_kernel(V) { return &k_wf_bounce<V::stats, V::lds, V::w4, V::sh, V::tri, V::cn, V::flat>; }
 
-// resident workgroups per CU of the kernel a form (1: k_wf_bounce, 2: k_seg) runs for this scene
+template <bool ANY, typename V>
+constexpr auto cast_kernel(V) { return &k_cast<ANY, V::lds, V::w4, V::sh, V::tri, V::cn, V::flat>; }
+
+// resident workgroups per CU of the kernel a form (1: k_wf_bounce, 2: k_seg; the ray queries: 3 k_cast
+// closest hit, 4 k_cast any hit) runs for this scene
 hipError_t wf_occupancy(const DevScene& sc, XVariant var, bool flat, size_t lds_bytes, int form, int* per_cu) {
     hipError_t e = hipSuccess;
     wf_dispatch(sc, var, flat, false, [&](auto V) {
-        const void* f = form == 2 ? reinterpret_cast<const void*>(seg_kernel(V)) : reinterpret_cast<const void*>(bounce_kernel(V));
+        const void* f = form == 4   ? reinterpret_cast<const void*>(cast_kernel<true>(V))
+                        : form == 3 ? reinterpret_cast<const void*>(cast_kernel<false>(V))
+                        : form == 2 ? reinterpret_cast<const void*>(seg_kernel(V))
+                                    : reinterpret_cast<const void*>(bounce_kernel(V));
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, f, 256, lds_bytes);
     });
     return e;
@@ -1006,6 +1093,21 @@ hipError_t launch_x_query_kat(const DevScene& sc, XVariant var, bool flat, size_
     wf_dispatch(sc, var, flat, false, [&](auto V) {
         using T = decltype(V);
         hipLaunchKernelGGL((k_x_query_kat<T::lds, T::w4, T::sh, T::tri, T::cn, T::flat>), grid, block, lds_bytes, stream, sc, cam_pos, n, recs, oi, od);
+    });
+    return hipGetLastError();
+}
+
+// The ray queries' launch: k_seg's variant for the scene (wf_dispatch) over a persistent grid of at most
+// `resident` workgroups (wf_occupancy forms 3 / 4), fewer when the rays need fewer.  Asynchronous on
+// `stream`; no allocation, no copy, no synchronisation.
+hipError_t launch_cast(const DevScene& sc, XVariant var, bool flat, size_t lds_bytes, int resident, bool any, const CastIO& io,
+                       hipStream_t stream) {
+    if (io.n <= 0) return hipSuccess;
+    const long long want = (io.n + 255) / 256;
+    const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>(want, resident))), block(256);
+    wf_dispatch(sc, var, flat, false, [&](auto V) {
+        if (any) hipLaunchKernelGGL(cast_kernel<true>(V), grid, block, lds_bytes, stream, sc, io);
+        else hipLaunchKernelGGL(cast_kernel<false>(V), grid, block, lds_bytes, stream, sc, io);
     });
     return hipGetLastError();
 }

@@ -15,6 +15,9 @@
  *   gi_render_device     the same frame into device-resident buffers on a HIP stream (bench,
  *                        multi-GPU tile sharding)
  *   gi_trace_ray         one iteration of raytracer.h:41-84 for an arbitrary ray
+ *   gi_intersect*        batched ray queries over the Mode X acceleration structure (no reference
+ *   gi_occluded*         counterpart): closest hit / any hit of caller-supplied rays, from host buffers
+ *                        or device-resident on a HIP stream
  *   gi_unshard_device    reassembles a frame from per-rank packed tiles after the RCCL gather
  *   gi_scene_kernel_ms   HIP-event duration of the last timed render's dominant kernel (bench)
  *   gi_scene_x_form      which Mode X form (persistent kernel / wavefront) a render would run
@@ -45,7 +48,7 @@
 extern "C" {
 #endif
 
-#define GI_ABI_VERSION 11
+#define GI_ABI_VERSION 12
 
 typedef enum gi_status {
     GI_OK = 0,
@@ -260,6 +263,47 @@ int gi_unshard_device(int w, int h, int shard_count, const double* d_packed, con
  * Ray ctor normalises it), light.  rgb receives the shaded colour (0 if no hit). */
 int gi_trace_ray(gi_scene* scene, const double origin[3], const double dir[3], const double light[3],
                  gi_hit* hit, double rgb[3]);
+
+/* ---- batched ray queries (ABI 12) ------------------------------------------------------------
+ * What does this ray hit?  n rays against the scene's Mode X acceleration structure, answered by the
+ * kernel variant a Mode X render of the scene runs (gi_kat_x_variant(scene, 0, ...) describes it).
+ *
+ * A ray is GI_RAY_DOUBLES = 8 doubles (64 bytes): o[3], d[3], tmax, reserved.  d is used as given: it
+ * is not normalised, and t is in units of d.  tmax may be +inf.  reserved is ignored.
+ *
+ * gi_intersect*: the closest hit -- the (t, primitive) minimum over t in (1e-7, tmax), ties to the
+ * lower primitive index.  gi_occluded*: any hit -- occluded = 1 when some primitive has t in
+ * (1e-7, tmax), else 0.
+ *   Range of t   open on both sides: a tmax equal to the closest hit's t is a miss (the strictness
+ *                the renders' own queries have).  tmax <= 1e-7 is a miss by the interval alone.
+ *   prim         Mode X's primitive numbering, as gi_kat_x_query documents it: entities in push
+ *                order, a meshed entity (ExpQuad, ExpCube, ...) as its triangles.
+ *   entity       that primitive's entity (push order).
+ *   normal       n*3: the unit geometric normal at the hit, flipped to face the ray (dot(d, normal)
+ *                <= 0) -- the normal Mode X shades with.
+ *   Miss         prim = entity = -1, t = +inf, normal = (0, 0, 0).
+ *   Outputs      any output pointer of gi_intersect* may be NULL and is then not written; all four
+ *                NULL is GI_ERR_ARG.
+ *   Malformed    a ray with a non-finite component of o or d, a zero d or a NaN tmax is screened
+ *                before any traversal and reported as a miss (occluded = 0); the other rays of the
+ *                call are not affected.
+ *   Arguments    n == 0 launches nothing and returns GI_OK; n < 0 is GI_ERR_ARG; NULL rays with
+ *                n > 0 is GI_ERR_ARG.  Device ray records are 16-byte aligned (GI_ERR_ARG otherwise).
+ * The _device variants take device pointers and are asynchronous on `stream` (hipStream_t; NULL =
+ * default stream): they make no allocation, no host synchronisation and no copy.  gi_intersect and
+ * gi_occluded do the same from / into host buffers (stage, launch, copy back) and are synchronous.
+ * Scene state: the queries read only the scene's immutable records.  They touch none of the scene's
+ * Mode X scratch (work list, counters, per-sample radiance rows) and are not ordered against the
+ * scene's renders, so they may run concurrently with a render and with each other on any streams,
+ * and a query between two progressive passes (gi_opts sample_begin / sample_end) does not end the
+ * progressive frame. */
+#define GI_RAY_DOUBLES 8
+int gi_intersect_device(gi_scene* scene, int64_t n, const double* d_rays, double* d_t, int32_t* d_prim,
+                        int32_t* d_entity, double* d_normal, void* stream);
+int gi_occluded_device(gi_scene* scene, int64_t n, const double* d_rays, int32_t* d_occluded, void* stream);
+int gi_intersect(gi_scene* scene, int64_t n, const double* rays, double* t, int32_t* prim, int32_t* entity,
+                 double* normal);
+int gi_occluded(gi_scene* scene, int64_t n, const double* rays, int32_t* occluded);
 
 /* Average duration in ms of the dominant kernel over the scene's renders issued with GI_FLAG_TIME
  * since the previous call (waits for the last one; *n = how many, may be NULL), then resets.
