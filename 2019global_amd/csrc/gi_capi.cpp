@@ -516,9 +516,10 @@ int scene_create_on(const gi_scene_desc* desc, int device, gi_scene** out) {
         // the flat leaf query (gi_wf.hip wf_flat): scenes staged in LDS whose leaf table fits
         d.n_xflat = (int32_t)h.xflat.size();
         d.x_flat = (d.x_lds_bytes > 0 && h.x_flat_ok) ? 1 : 0;
-        // light shading (no acos texture mapping, no sphere primitives): 4 waves per SIMD pay off,
-        // provided four workgroups fit a CU's 160 KB: each holds the scene, the per-lane path slots
-        // (256 lanes x 80 B) and the per-wave unit blocks (4 x 68 x 4 B)
+        // light shading (no acos texture mapping, no sphere primitives): gi_wf.hip's kernels (k_seg, k_cast)
+        // run 4 waves per SIMD, provided four workgroups fit a CU's 160 KB.  The bound allows each, beside
+        // the scene, 256 lanes x 80 B and 4 x 68 x 4 B -- more than their path slots (256 x 72 B) need: it
+        // is the footprint of the LDS build k_mode_x once had, kept so that no scene changes its variant
         const size_t per_wg = bytes + 256 * 10 * sizeof(double) + 4 * 68 * sizeof(unsigned);
         d.x_waves4 = (d.x_lds_bytes > 0 && 4 * per_wg <= 160 * 1024) ? 1 : 0;
         d.x_tri_only = 1;

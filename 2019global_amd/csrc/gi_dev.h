@@ -553,37 +553,5 @@ __device__ __forceinline__ void x_texcoord(const DevScene& sc, const REnt& e, V3
     }
 }
 
-#ifndef GI_XFLAT_LDS
-#define GI_XFLAT_LDS 0   // (A/B builds) 1: gi_wf.hip's flat query reads a copy of its leaf table staged in LDS
-#endif
-// An LDS-resident scene (sc.x_lds_bytes > 0) as a workgroup stages it at the start of its dynamic LDS:
-// traversal records (wide nodes, leaf records) and shading records (primitives, entities), so neither
-// the traversal nor the shading issues a global load.  FT (FLAT_TAB: the flat leaf table too, after the
-// entities; else the scene's table in global memory); end: the first int4 after the staged records.
-struct XStaged { const XWNode* W; const XHot* H; const XPrim* XP; const REnt* EN; const XFlatLeaf* FT; int4* end; };
-template <bool FLAT_TAB>
-__device__ __forceinline__ XStaged x_stage_lds(const DevScene& sc, int4* lds) {
-    const int nw = sc.n_xwnodes * (int)(sizeof(XWNode) / sizeof(int4));
-    const int nh = sc.n_xhot * (int)(sizeof(XHot) / sizeof(int4));
-    const int np = sc.n_xprims * (int)(sizeof(XPrim) / sizeof(int4));
-    const int ne = sc.n_ents * (int)(sizeof(REnt) / sizeof(int4));
-    const int nf = FLAT_TAB ? sc.n_xflat * (int)(sizeof(XFlatLeaf) / sizeof(int4)) : 0;
-    const int4* gw = reinterpret_cast<const int4*>(sc.xwnodes);
-    const int4* gh = reinterpret_cast<const int4*>(sc.xhot);
-    const int4* gp = reinterpret_cast<const int4*>(sc.xprims);
-    const int4* ge = reinterpret_cast<const int4*>(sc.ents);
-    const int4* gf = reinterpret_cast<const int4*>(sc.xflat);
-    for (int i = threadIdx.x; i < nw; i += blockDim.x) lds[i] = gw[i];
-    for (int i = threadIdx.x; i < nh; i += blockDim.x) lds[nw + i] = gh[i];
-    for (int i = threadIdx.x; i < np; i += blockDim.x) lds[nw + nh + i] = gp[i];
-    for (int i = threadIdx.x; i < ne; i += blockDim.x) lds[nw + nh + np + i] = ge[i];
-    for (int i = threadIdx.x; i < nf; i += blockDim.x) lds[nw + nh + np + ne + i] = gf[i];
-    __syncthreads();
-    return XStaged{reinterpret_cast<const XWNode*>(lds), reinterpret_cast<const XHot*>(lds + nw),
-                   reinterpret_cast<const XPrim*>(lds + nw + nh), reinterpret_cast<const REnt*>(lds + nw + nh + np),
-                   FLAT_TAB ? reinterpret_cast<const XFlatLeaf*>(lds + nw + nh + np + ne) : sc.xflat,
-                   lds + nw + nh + np + ne + nf};
-}
-
 }  // namespace
 }  // namespace gi

@@ -1250,10 +1250,7 @@ enum : int { PH_CLOSEST = 0, PH_SHADOW = 1, PH_NEED = 2, PH_START = 3, PH_DEAD =
 #define GI_X_START_BURST 16   // primary rays a lane may resolve by the root test per handler run
 #endif
 #ifndef GI_X_MIN_WAVES
-#define GI_X_MIN_WAVES 3       // minimum waves per SIMD, HBM-resident scenes (<= 168 VGPRs)
-#endif
-#ifndef GI_X_MIN_WAVES_LDS
-#define GI_X_MIN_WAVES_LDS 4   // LDS-resident scenes (<= 128 VGPRs; the few spills sit in the handler)
+#define GI_X_MIN_WAVES 3       // minimum waves per SIMD (<= 168 VGPRs)
 #endif
 
 struct XCounters {
@@ -1321,13 +1318,13 @@ __device__ __forceinline__ int nth_set_bit(unsigned long long m, unsigned n) {
     return __ffsll((long long)m) - 1;
 }
 
-// NST: the wide-node index of every level of the current traversal path lives in LDS (nst[level *
+// One wave of k_mode_x.  The traversal records are read from global memory: wide nodes W (XWNode, or
+// the quantised XCNode), leaf records H, shading records XP / EN.
+// nst: the wide-node index of every level of the current traversal path lives in LDS (nst[level *
 // 256], one column per lane), so climbing out of exhausted levels is one ds_read instead of a chain
 // of dependent parent-pointer loads from HBM / L2 (one per level climbed).
-template <bool STATS, bool PAIR, bool PSL, bool NST, bool HELP, bool SH, bool TRI, typename NodeP,
-          typename HotP, typename PrimP, typename EntP>
-__device__ __forceinline__ void mode_x_wave(const DevScene& sc, NodeP W, HotP H, PrimP XP, EntP EN, double* pslot,
-                                            int* nst, XHelp hp_,
+template <bool STATS, bool HELP, bool SH, bool TRI, typename NodeP, typename HotP, typename PrimP, typename EntP>
+__device__ __forceinline__ void mode_x_wave(const DevScene& sc, NodeP W, HotP H, PrimP XP, EntP EN, int* nst, XHelp hp_,
                                             const CamDev& cam, V3 light,
                                             const TileMap& m, int spp, int depth, uint64_t seed, double* rgb,
                                             uint8_t* rgb8, unsigned* blk_list, const XWork& wk, int handle8,
@@ -1386,18 +1383,12 @@ __device__ __forceinline__ void mode_x_wave(const DevScene& sc, NodeP W, HotP H,
     V3 o = cam.pos, d = v3(1, 0, 0);
     int dmask = 0, best = -1, node = 0, level = 0;
     bool raying = false;
-    // MERGE (LDS kernel): the step's interior-node test and a restarted ray's root test share one
-    // children_mask call at the end of the step
-    constexpr bool MERGE = PAIR && PSL && !NST;
-    // UL (quantised-node HBM scenes): one load round trip per step for the node-test and leaf-test
-    // lanes together
+    // UL (quantised nodes): one load round trip per step for the node-test and leaf-test lanes
+    // together
     // (round 5: in the build without the shadow handoff -- long launches, C5 -- the merged round
     // trip costs more than it saves: C5 178.3 -> 176.8 ms without it, C4 +2% without it, so it stays
     // in the handoff build only)
-    constexpr bool UL = !PAIR && HELP &&
-                        std::is_same<std::remove_cv_t<std::remove_pointer_t<NodeP>>, XCNode>::value;
-    bool desc = false, rs = false;   // MERGE: this step descends into xch / restarts at the root
-    int xch = 0;
+    constexpr bool UL = HELP && std::is_same<std::remove_cv_t<std::remove_pointer_t<NodeP>>, XCNode>::value;
     uint64_t mlo = 0, mhi = 0;
     double tbest = INFINITY, tmax = INFINITY;
     float tbest_f = INFINITY;
@@ -1409,10 +1400,9 @@ __device__ __forceinline__ void mode_x_wave(const DevScene& sc, NodeP W, HotP H,
     V3 nextd = v3(0, 0, 0);   // carried across the shadow ray (its origin = the shadow ray's)
     bool has_next = false;
 
-    // fp64 primitive tests of one leaf's records hp[0 .. cntl) (these decide the result): global
-    // records fetched one ahead of the test; LDS records (PAIR) two at a time, the two fp64
-    // dependency chains interleaved.  A shadow ray (own or a helper's) stops at any hit.
-    // leaf_test_from: global records, the first one already in registers (cur; UL below)
+    // fp64 primitive tests of one leaf's records hp[0 .. cntl) (these decide the result), each
+    // fetched one ahead of its test; the first one is already in registers (cur: UL below issues
+    // that load itself).  A shadow ray (own or a helper's) stops at any hit.
     auto leaf_test_from = [&](XHotR cur, const auto* hp, int cntl) {
         for (int j = 0; j < cntl; ++j) {
             const XHotR rec = cur;
@@ -1432,41 +1422,14 @@ __device__ __forceinline__ void mode_x_wave(const DevScene& sc, NodeP W, HotP H,
             }
         }
     };
-    auto leaf_test = [&](const auto* hp, int cntl) {
-        if constexpr (!PAIR) {
-            leaf_test_from(load_hot(hp), hp, cntl);
-        } else {
-            for (int j = 0; j < cntl; j += 2) {
-                const bool two = j + 1 < cntl;
-                const XHotR r0 = load_hot(hp + j), r1 = load_hot(hp + (two ? j + 1 : j));
-                const double ta = x_prim_t<TRI>(r0.h, o, d, MX_TMIN);
-                const double tb = two ? x_prim_t<TRI>(r1.h, o, d, MX_TMIN) : INFINITY;
-                nprim += two ? 2 : 1;
-                if (phase != PH_CLOSEST) {
-                    if ((ta < tmax) | (tb < tmax)) {   // any hit occludes
-                        best = ta < tmax ? r0.h.prim : r1.h.prim;
-                        raying = false;
-                        return;
-                    }
-                } else {   // (selects, not branches)
-                    const bool ua = (ta < tbest) | ((ta == tbest) & (r0.h.prim < best));
-                    tbest = ua ? ta : tbest;
-                    best = ua ? r0.h.prim : best;
-                    const bool ub = (tb < tbest) | ((tb == tbest) & (r1.h.prim < best));
-                    tbest = ub ? tb : tbest;
-                    best = ub ? r1.h.prim : best;
-                    tbest_f = up32(tbest);
-                }
-            }
-        }
-    };
+    // the same from the first record's load on.  (Kept a lambda: written out at its call site the
+    // compiler orders 28 of the 32 kernels' instructions and registers differently -- DESIGN.md §5.)
+    auto leaf_test = [&](const auto* hp, int cntl) { leaf_test_from(load_hot(hp), hp, cntl); };
 
-
-    // PF (HBM-resident scenes): the next pop's child reference and leaf count are fetched at the
-    // end of the step that sets up the level (descend, climb or ray start), so the pop itself waits
-    // for no load: one dependent round trip per step (the child's node or leaf records) instead of
-    // two.  (lvl mask, node) do not change between that fetch and the pop.
-    constexpr bool PF = !PAIR;   // (LDS-resident scenes: a ds_read away; +3% with PF)
+    // The next pop's child reference and leaf count are fetched at the end of the step that sets up
+    // the level (descend, climb or ray start), so the pop itself waits for no load: one dependent
+    // round trip per step (the child's node or leaf records) instead of two.  (lvl mask, node) do
+    // not change between that fetch and the pop.
     int pf_ch = 0, pf_cnt = 0;
     auto prefetch = [&]() {
         const uint32_t m = lvl_get<SH>(mlo, mhi, level);
@@ -1498,11 +1461,11 @@ __device__ __forceinline__ void mode_x_wave(const DevScene& sc, NodeP W, HotP H,
                 tbest_f = up32(tmax);
                 phase = PH_HELP;
                 best = -1;
-                const uint32_t rm = children_mask<PAIR>(W, of, ivf, tbest_f, dmask);
+                const uint32_t rm = children_mask<false>(W, of, ivf, tbest_f, dmask);
                 node = 0;
                 lvl_set<SH>(mlo, mhi, 0, rm);
                 raying = rm != 0;
-                if (PF && raying) prefetch();
+                if (raying) prefetch();
             }
         }
         const unsigned long long m_live = __ballot(phase != PH_DEAD);
@@ -1538,24 +1501,18 @@ __device__ __forceinline__ void mode_x_wave(const DevScene& sc, NodeP W, HotP H,
             // ---- one traversal step (stackless: 8-bit "children left" mask per level).  Invariant:
             // the current level has a child left; the step pops it, then climbs past exhausted
             // levels, so a ray ends in the step that exhausts the root level (no empty iteration).
-            const auto* nd = W + node;
+            // The popped child (the lowest set bit: next in front-to-back order) and its leaf count
+            // were fetched by the step that set this level up (prefetch above).
             const uint32_t msk = lvl_get<SH>(mlo, mhi, level);
-            const int kc = __builtin_ctz(msk);         // next child in front-to-back order
             lvl_set<SH>(mlo, mhi, level, msk & (msk - 1));
-            const int c = kc ^ dmask;
-            const int ch = PF ? pf_ch : nd->child[c];
-            xch = ch;
-            desc = false;
-            // a closer hit may have arrived since the mask was computed: re-cull this child -- in
-            // the LDS kernel only: in HBM-resident scenes an interior child's own node test culls its
-            // children against the same t, and skipping the re-cull drops a node-record fetch and ~60
-            // instructions from the step (round 3: C5 214 -> 199 ms, C4 1.96 -> 1.82; leaves: their
-            // fp64 tests run against the best t as it stands; the LDS kernel, whose re-cull is cheaper
-            // than a node test, keeps it: C3 +0.9% without)
-            bool keep = true;
-            if (PAIR && phase == PH_CLOSEST && best >= 0) keep = child_hit(nd, c, of, ivf, tbest_f);
+            const int ch = pf_ch;
+            // A closer hit may have arrived since the mask was computed, but the child is not
+            // re-culled against it: an interior child's own node test culls its children against the
+            // same t, a leaf's fp64 tests run against the best t as it stands, and the re-cull would
+            // cost a node-record fetch and ~60 instructions per step (round 3: C5 214 -> 199 ms, C4
+            // 1.96 -> 1.82 without it).
             if (STATS) {
-                const unsigned long long mn = __ballot(keep && ch >= 0), ml = __ballot(keep && ch < 0);
+                const unsigned long long mn = __ballot(ch >= 0), ml = __ballot(ch < 0);
                 if (lane == 0) {
                     cnt.it_node += mn != 0;
                     cnt.ln_node += __popcll(mn);
@@ -1563,13 +1520,13 @@ __device__ __forceinline__ void mode_x_wave(const DevScene& sc, NodeP W, HotP H,
                     cnt.ln_leaf += __popcll(ml);
                 }
             }
-            if (UL) {   // (keep is always true in HBM-resident scenes: no re-cull)
+            if (UL) {
                 // one memory round trip for the wave's node-test AND leaf-test lanes: each lane's
                 // load (the child's 64 slab bytes, or its leaf's first record) is issued before
                 // either test waits, instead of a node-test block and a leaf-test block each
                 // waiting on its own load
                 XHotR ur;
-                const int cntl = ch < 0 ? (PF ? pf_cnt : (int)nd->cnt[c]) : 0;
+                const int cntl = ch < 0 ? pf_cnt : 0;
                 if (ch < 0) {
                     ur = load_hot(H + ~ch);
                 } else {
@@ -1587,46 +1544,34 @@ __device__ __forceinline__ void mode_x_wave(const DevScene& sc, NodeP W, HotP H,
                         node = ch;
                         ++level;
                         lvl_set<SH>(mlo, mhi, level, cm);
-                        if (NST) nst[level * 256] = ch;
+                        nst[level * 256] = ch;
                     }
                 }
-            } else if (keep) {
-                if (ch < 0) {             // leaf: fp64 primitive tests (these decide the result)
-                    leaf_test(H + ~ch, PF ? pf_cnt : (int)nd->cnt[c]);
-                } else if (MERGE) {       // the node test runs below, shared with the restarts
-                    desc = true;
-                } else {                  // descend if any of the child's 8 children is hit (fp32)
-                    ++nnode;
-                    const uint32_t cm = children_mask<PAIR>(W + ch, of, ivf, tbest_f, dmask);
-                    if (cm) {
-                        node = ch;
-                        ++level;
-                        lvl_set<SH>(mlo, mhi, level, cm);
-                        if (NST) nst[level * 256] = ch;
-                    }
+            } else if (ch < 0) {      // leaf: fp64 primitive tests (these decide the result)
+                leaf_test(H + ~ch, pf_cnt);
+            } else {                  // descend if any of the child's 8 children is hit (fp32)
+                ++nnode;
+                const uint32_t cm = children_mask<false>(W + ch, of, ivf, tbest_f, dmask);
+                if (cm) {
+                    node = ch;
+                    ++level;
+                    lvl_set<SH>(mlo, mhi, level, cm);
+                    nst[level * 256] = ch;
                 }
             }
-            if (raying && !desc) {        // climb to the nearest level with children left
+            if (raying) {             // climb to the nearest level with children left
                 uint32_t rest = lvl_get<SH>(mlo, mhi, level);
-                if constexpr (NST) {
-                    if (rest == 0 && level > 0) {
-                        // the deepest level below with children left, by one leading-zero count
-                        const uint64_t lm = level >= 8 ? mlo : mlo & ((1ull << (8 * level)) - 1);
-                        const uint64_t hm = level <= 8 ? 0ull : mhi & ((1ull << (8 * (level - 8))) - 1);
-                        level = hm ? 8 + (63 - __clzll((long long)hm)) / 8 : lm ? (63 - __clzll((long long)lm)) / 8 : 0;
-                        rest = lvl_get<SH>(mlo, mhi, level);
-                        node = level == 0 ? 0 : nst[level * 256];
-                    }
-                } else {
-                    while (rest == 0 && level > 0) {
-                        --level;
-                        node = level == 0 ? 0 : W[node].parent;   // the root is node 0: no load
-                        rest = lvl_get<SH>(mlo, mhi, level);
-                    }
+                if (rest == 0 && level > 0) {
+                    // the deepest level below with children left, by one leading-zero count
+                    const uint64_t lm = level >= 8 ? mlo : mlo & ((1ull << (8 * level)) - 1);
+                    const uint64_t hm = level <= 8 ? 0ull : mhi & ((1ull << (8 * (level - 8))) - 1);
+                    level = hm ? 8 + (63 - __clzll((long long)hm)) / 8 : lm ? (63 - __clzll((long long)lm)) / 8 : 0;
+                    rest = lvl_get<SH>(mlo, mhi, level);
+                    node = level == 0 ? 0 : nst[level * 256];
                 }
                 if (rest == 0) raying = false;   // ray finished
             }
-            if (PF && raying && !desc) prefetch();   // (MERGE: descending lanes below)
+            if (raying) prefetch();
             // a finished shadow ray whose path continues: resolve it and start the next bounce
             // right here (the bounce direction was drawn when the hit was shaded), so the lane
             // keeps traversing instead of waiting for the shading handler (short-traversal scenes;
@@ -1640,8 +1585,8 @@ __device__ __forceinline__ void mode_x_wave(const DevScene& sc, NodeP W, HotP H,
             }
             if (inline_shadow && !raying && phase == PH_SHADOW && has_next) {
                 ++nrays;
-                if (best >= 0) Lv = PSL ? v3(pslot[0], pslot[1], pslot[2]) : Lo;   // occluded: ambient term only
-                d = PSL ? v3(pslot[3], pslot[4], pslot[5]) : nextd;                // o is still the hit point
+                if (best >= 0) Lv = Lo;   // occluded: ambient term only
+                d = nextd;                // o is still the hit point
                 ++b;
                 phase = PH_CLOSEST;
                 tmax = INFINITY;
@@ -1651,46 +1596,13 @@ __device__ __forceinline__ void mode_x_wave(const DevScene& sc, NodeP W, HotP H,
                 ivf = inv_dir(d);
                 dmask = (d.x < 0 ? 1 : 0) | (d.y < 0 ? 2 : 0) | (d.z < 0 ? 4 : 0);
                 best = -1;
-                if (MERGE) {         // the root test runs in the shared node test below
-                    rs = true;
-                } else {
-                    const uint32_t rm = children_mask<PAIR>(W, of, ivf, tbest_f, dmask);
-                    node = 0;
-                    level = 0;
-                    mlo = mhi = 0;
-                    lvl_set<SH>(mlo, mhi, 0, rm);
-                    raying = rm != 0;
-                    if (PF && raying) prefetch();
-                }
-            }
-            // MERGE: one node test per step for the lanes that descend into an interior child and
-            // the lanes whose next bounce starts here (the root) -- one block instead of two
-            if (MERGE && (desc || rs)) {
-                if (desc) ++nnode;
-                const uint32_t cm = children_mask<PAIR>(W + (rs ? 0 : xch), of, ivf, tbest_f, dmask);
-                if (rs) {
-                    node = 0;
-                    level = 0;
-                    mlo = mhi = 0;
-                    lvl_set<SH>(mlo, mhi, 0, cm);
-                    raying = cm != 0;
-                } else if (cm) {
-                    node = xch;
-                    ++level;
-                    lvl_set<SH>(mlo, mhi, level, cm);
-                } else {   // the child's children all missed: climb as an unmerged step would have
-                    uint32_t rest = lvl_get<SH>(mlo, mhi, level);
-                    while (rest == 0 && level > 0) {
-                        --level;
-                        node = level == 0 ? 0 : W[node].parent;
-                        rest = lvl_get<SH>(mlo, mhi, level);
-                    }
-                    // a ray that ends here waits for the handler (which continues a shadow ray's path)
-                    if (rest == 0) raying = false;
-                }
-                if (PF && raying) prefetch();
-                rs = false;
-                desc = false;
+                const uint32_t rm = children_mask<false>(W, of, ivf, tbest_f, dmask);
+                node = 0;
+                level = 0;
+                mlo = mhi = 0;
+                lvl_set<SH>(mlo, mhi, 0, rm);
+                raying = rm != 0;
+                if (raying) prefetch();
             }
         }
         const uint64_t t1 = STATS ? clock64() : 0;
@@ -1708,7 +1620,7 @@ __device__ __forceinline__ void mode_x_wave(const DevScene& sc, NodeP W, HotP H,
                 if (r == 0) {
                     hold = true;
                 } else {
-                    if (r == 2) Lv = PSL ? v3(pslot[0], pslot[1], pslot[2]) : Lo;   // occluded: ambient only
+                    if (r == 2) Lv = Lo;   // occluded: ambient only
                     hp_.res[tid] = 0;
                     pend = false;
                 }
@@ -1740,27 +1652,22 @@ __device__ __forceinline__ void mode_x_wave(const DevScene& sc, NodeP W, HotP H,
                     const double spw = mx_pow(smax(0.0, dot(N, bis)), e.spec_pow);
                     const V3 ls = v3(spw, spw, spw) * e.shader[2];
                     const V3 lo = (la + ldf) + ls;
-                    if (PSL) T = v3(pslot[6], pslot[7], pslot[8]);
                     Lo = Lv + vmul(T, v3(smin(la.x, 1.0), smin(la.y, 1.0), smin(la.z, 1.0)));
-                    if (PSL) { pslot[0] = Lo.x; pslot[1] = Lo.y; pslot[2] = Lo.z; }
                     Lv = Lv + vmul(T, v3(smin(lo.x, 1.0), smin(lo.y, 1.0), smin(lo.z, 1.0)));
                     has_next = false;
                     // mirror bounce with probability e.refl (uniform dim 4): T unchanged, d reflected
                     // about the facing normal; otherwise the diffuse bounce below
                     const bool mirror = b != depth - 1 && e.refl > 0.0 &&
-                                        mx_u01k(PSL ? reinterpret_cast<const uint64_t*>(pslot)[9] : key, smp, b, 4) < e.refl;
+                                        mx_u01k(key, smp, b, 4) < e.refl;
                     if (mirror) {
                         nextd = normalize(din - N * (2.0 * dot(din, N)));
-                        if (PSL) { pslot[3] = nextd.x; pslot[4] = nextd.y; pslot[5] = nextd.z; }
                         has_next = true;
                     } else if (b != depth - 1) {
                         const V3 Tn = vmul(T, tc * 0.5);
                         T = Tn;
-                        if (PSL) { pslot[6] = Tn.x; pslot[7] = Tn.y; pslot[8] = Tn.z; }
                         if (!(Tn.x == 0.0 && Tn.y == 0.0 && Tn.z == 0.0)) {
                             double sx, sy, r2;   // cosine-weighted: concentric disk + Malley
-                            const uint64_t kk = PSL ? reinterpret_cast<const uint64_t*>(pslot)[9] : key;
-                            mx_disk(mx_u01k(kk, smp, b, 2), mx_u01k(kk, smp, b, 3), sx, sy, r2);
+                            mx_disk(mx_u01k(key, smp, b, 2), mx_u01k(key, smp, b, 3), sx, sy, r2);
                             const double sz = gsqrt(1.0 - r2);
                             const double sg = N.z >= 0.0 ? 1.0 : -1.0;
                             const double aa = -1.0 / (sg + N.z);
@@ -1768,7 +1675,6 @@ __device__ __forceinline__ void mode_x_wave(const DevScene& sc, NodeP W, HotP H,
                             const V3 bt1 = v3(1.0 + sg * N.x * N.x * aa, sg * bb, -sg * N.x);
                             const V3 bt2 = v3(bb, sg + N.y * N.y * aa, -N.y);
                             nextd = normalize((bt1 * sx + bt2 * sy) + N * sz);
-                            if (PSL) { pslot[3] = nextd.x; pslot[4] = nextd.y; pslot[5] = nextd.z; }
                             has_next = true;
                         }
                     }
@@ -1791,7 +1697,7 @@ __device__ __forceinline__ void mode_x_wave(const DevScene& sc, NodeP W, HotP H,
                                 pend = true;
                                 gave = true;
                                 o = P;
-                                d = PSL ? v3(pslot[3], pslot[4], pslot[5]) : nextd;
+                                d = nextd;
                                 ++b;
                                 phase = PH_CLOSEST;
                                 tmax = INFINITY;
@@ -1811,11 +1717,11 @@ __device__ __forceinline__ void mode_x_wave(const DevScene& sc, NodeP W, HotP H,
                 }
             } else if (phase == PH_SHADOW) {
                 ++nrays;
-                if (best >= 0) Lv = PSL ? v3(pslot[0], pslot[1], pslot[2]) : Lo;   // occluded: ambient term only
+                if (best >= 0) Lv = Lo;   // occluded: ambient term only
                 if (!has_next) {
                     end_path = true;
                 } else {
-                    d = PSL ? v3(pslot[3], pslot[4], pslot[5]) : nextd;   // o is still the hit point
+                    d = nextd;   // o is still the hit point
                     ++b;
                     phase = PH_CLOSEST;
                     tmax = INFINITY;
@@ -1923,7 +1829,6 @@ __device__ __forceinline__ void mode_x_wave(const DevScene& sc, NodeP W, HotP H,
                             y += m.y0;
                             if (spp > 1) idx = (long long)i;        // per-sample radiance row
                             key = mx_key(seed, (uint64_t)y * (uint64_t)m.w + (uint64_t)x);
-                            if (PSL) reinterpret_cast<uint64_t*>(pslot)[9] = key;
                             smp = wk.s0 + (int)cu * k;
                             phase = PH_START;
                             if (cu == 0) ++npx;
@@ -1935,9 +1840,8 @@ __device__ __forceinline__ void mode_x_wave(const DevScene& sc, NodeP W, HotP H,
                 if (phase == PH_START) {
                     double jx = 0.0, jy = 0.0;
                     if (spp > 1) {
-                        const uint64_t kk = PSL ? reinterpret_cast<const uint64_t*>(pslot)[9] : key;
-                        jx = mx_u01k(kk, smp, 0xFFFF, 0);
-                        jy = mx_u01k(kk, smp, 0xFFFF, 1);
+                        jx = mx_u01k(key, smp, 0xFFFF, 0);
+                        jy = mx_u01k(key, smp, 0xFFFF, 1);
                     }
                     const V3 d0 = primary_dir(cam, (double)x + jx, (double)y + jy);
                     if (burst < GI_X_START_BURST) {
@@ -1970,7 +1874,6 @@ __device__ __forceinline__ void mode_x_wave(const DevScene& sc, NodeP W, HotP H,
                     d = normalize(d0);
                     Lv = v3(0, 0, 0);
                     T = v3(1, 1, 1);
-                    if (PSL) { pslot[6] = 1.0; pslot[7] = 1.0; pslot[8] = 1.0; }
                     b = 0;
                     tmax = INFINITY;
                     tbest = INFINITY;
@@ -1986,7 +1889,7 @@ __device__ __forceinline__ void mode_x_wave(const DevScene& sc, NodeP W, HotP H,
                 of = f3((float)o.x, (float)o.y, (float)o.z);
                 ivf = inv_dir(d);
                 dmask = (d.x < 0 ? 1 : 0) | (d.y < 0 ? 2 : 0) | (d.z < 0 ? 4 : 0);
-                const uint32_t rm = children_mask<PAIR>(W, of, ivf, tbest_f, dmask);
+                const uint32_t rm = children_mask<false>(W, of, ivf, tbest_f, dmask);
                 if (phase == PH_START) phase = PH_CLOSEST;
                 best = -1;
                 node = 0;   // root wide node
@@ -1994,7 +1897,7 @@ __device__ __forceinline__ void mode_x_wave(const DevScene& sc, NodeP W, HotP H,
                 mlo = mhi = 0;
                 lvl_set<SH>(mlo, mhi, 0, rm);
                 raying = rm != 0;   // no root child hit: finished (consumed by the next handler run)
-                if (PF && raying) prefetch();
+                if (raying) prefetch();
                 break;
             }
         }
@@ -2022,58 +1925,37 @@ __device__ __forceinline__ void mode_x_wave(const DevScene& sc, NodeP W, HotP H,
 // Persistent waves: the grid is sized to the resident capacity; every lane pulls pixel slots
 // from one device counter (SURVEY §7 hard part 4: per-ray cost varies ~10x between background
 // and scene pixels), so no lane idles behind a sibling, a workgroup or the grid tail.
-// LDS: small scenes (sc.x_lds_bytes > 0) keep the whole traversal structure -- wide nodes and
-// leaf records -- in LDS, copied once by each resident workgroup; every traversal load is then a
-// ds_read instead of a vector-memory round trip.
-// W4, LDS-resident scenes (XVariant::w4): 4 waves per SIMD (<= 128 VGPRs) for scenes whose shading is
-// light (triangles without acos texture mapping: +7% on the Cornell box); scenes with spheres / cones /
-// rectangles keep 3 (their heavier handler spills at 128 VGPRs: -45% on the main.cpp scene at 4).
-// W4, HBM-resident scenes (XVariant::help): the same template parameter selects the shadow-ray handoff
-// build (XHelp), chosen per launch for small launches, whose frame time is their longest paths' latency
-// (C4: 3.01 -> 2.64 ms, with spread work groups 2.40 ms); in long launches (C5) the handoff build's
-// heavier code costs 8%, so they run without.
-// CN (HBM-resident scenes): traverse the quantised nodes (DevScene::xcnodes) instead of XWNode.
-// TR (HBM-resident scenes): the scene is triangle meshes of the 4-wave kinds only (DevScene::x_tri_only,
-// e.g. the 100k soup): mode_x_wave's TRI specialisation (LDS-resident scenes: theirs is W4).
-// x_dispatch (below) names the instantiations that are launched: LDS, W4 x SH; HBM, HELP x CN x SH x TR.
-template <bool STATS, bool LDS, bool W4, bool CN, bool SH, bool TR = false>
-__global__ __launch_bounds__(256, (LDS && W4) ? GI_X_MIN_WAVES_LDS : GI_X_MIN_WAVES) void k_mode_x(DevScene sc, CamDev cam, V3 light, TileMap m, int spp, int depth,
+// The scene is read from global memory, whether or not it would fit in LDS: by default
+// (x_form_choice) the kernel runs large HBM-resident scenes only; a scene staged in LDS by k_seg
+// comes here only when the form is forced (GI_FLAG_X_MEGA, GI_X_WF=0) and is traversed like any other.
+// HELP (launch_render's rule): the shadow-ray handoff build (XHelp), chosen per launch for small launches,
+// whose frame time is their longest paths' latency (C4: 3.01 -> 2.64 ms, with spread work groups
+// 2.40 ms); in long launches (C5) the handoff build's heavier code costs 8%, so they run without.
+// CN: traverse the quantised nodes (DevScene::xcnodes) instead of XWNode.
+// SH: the per-level masks in one 64-bit word (trees of at most 8 levels).
+// TR: the scene is triangle meshes of the 4-wave kinds only (DevScene::x_tri_only, e.g. the 100k
+// soup): mode_x_wave's TRI specialisation.
+// x_dispatch (below) names the instantiations that are launched: STATS x HELP x CN x SH x TR.
+template <bool STATS, bool HELP, bool CN, bool SH, bool TR>
+__global__ __launch_bounds__(256, GI_X_MIN_WAVES) void k_mode_x(DevScene sc, CamDev cam, V3 light, TileMap m, int spp, int depth,
                                                  uint64_t seed, double* rgb, uint8_t* rgb8,
                                                  unsigned long long* stats, XWork wk, int handle8, int xflags) {
     XCounters c;
     __shared__ unsigned s_blk[kWavesPerBlock][68];   // per wave: current block's list entries + state
     unsigned* blk = s_blk[threadIdx.x >> 6];
-    if (LDS) {
-        extern __shared__ int4 lds_scene[];
-        // traversal records and shading records (primitives, entities) staged in LDS: the shading handler
-        // then issues no global load, so its waits never include the lane's outstanding stores
-        const XStaged s = x_stage_lds<false>(sc, lds_scene);
-        // 4-wave kernel: path values used only by the shading handler and at the shadow ray's end
-        // (occluded sum, next direction, throughput T, RNG key) live in a per-lane LDS slot after
-        // the scene instead of in VGPRs / scratch
-        double* pslot = reinterpret_cast<double*>(s.end) + 10 * threadIdx.x;
-        mode_x_wave<STATS, true, W4, false, false, SH, W4>(sc, s.W, s.H, s.XP, s.EN, pslot, nullptr, XHelp{},
-                                                                        cam, light, m, spp, depth, seed, rgb, rgb8, blk,
-                                                                        wk, handle8, xflags, c);
-    } else {
-        // dynamic LDS: the 16 levels x 256 lanes of node indices, then the handoff
-        // slots (7 x 256 doubles, 2 x 256 ints)
-        extern __shared__ int lds_nst[];
-        XHelp hp;
-        hp.ray = reinterpret_cast<double*>(lds_nst + 16 * 256);
-        hp.own = reinterpret_cast<int*>(hp.ray + 7 * 256);
-        hp.res = hp.own + 256;
-        if constexpr (CN)   // quantised nodes (the default for large HBM-resident scenes)
-            mode_x_wave<STATS, false, false, true, W4, SH, TR>(sc, sc.xcnodes, sc.xhot, sc.xprims,
-                                                                            sc.ents, nullptr, lds_nst + threadIdx.x, hp,
-                                                                            cam, light, m, spp, depth, seed, rgb, rgb8,
-                                                                            blk, wk, handle8, xflags, c);
-        else
-            mode_x_wave<STATS, false, false, true, W4, SH, TR>(sc, sc.xwnodes, sc.xhot, sc.xprims,
-                                                                            sc.ents, nullptr, lds_nst + threadIdx.x, hp,
-                                                                            cam, light, m, spp, depth, seed, rgb, rgb8,
-                                                                            blk, wk, handle8, xflags, c);
-    }
+    // dynamic LDS: the 16 levels x 256 lanes of node indices, then the handoff
+    // slots (7 x 256 doubles, 2 x 256 ints)
+    extern __shared__ int lds_nst[];
+    XHelp hp;
+    hp.ray = reinterpret_cast<double*>(lds_nst + 16 * 256);
+    hp.own = reinterpret_cast<int*>(hp.ray + 7 * 256);
+    hp.res = hp.own + 256;
+    if constexpr (CN)   // quantised nodes (the default for large HBM-resident scenes)
+        mode_x_wave<STATS, HELP, SH, TR>(sc, sc.xcnodes, sc.xhot, sc.xprims, sc.ents, lds_nst + threadIdx.x, hp, cam, light, m,
+                                         spp, depth, seed, rgb, rgb8, blk, wk, handle8, xflags, c);
+    else
+        mode_x_wave<STATS, HELP, SH, TR>(sc, sc.xwnodes, sc.xhot, sc.xprims, sc.ents, lds_nst + threadIdx.x, hp, cam, light, m,
+                                         spp, depth, seed, rgb, rgb8, blk, wk, handle8, xflags, c);
     if (STATS) {
         if ((threadIdx.x & 63) == 0) {
             atomicAdd(stats + GI_STAT_X_ITERS, (unsigned long long)c.iters);
@@ -2340,37 +2222,26 @@ int r_kernel_choice(const DevScene& sc, const gi_opts& o) {
     return (env.r_flat == 2 || (unsigned)sc.n_ents > kRfEntMask) ? 2 : 1;
 }
 
-// The k_mode_x instantiation a launch runs: f(XTag) for the scene and the variant.  LDS-resident scenes:
-// W4 x SH; HBM-resident ones: HELP x CN x SH x TR -- with STATS the 40 instantiations of the library.
-// SH: the per-level masks in one 64-bit word when the tree has at most 8 levels.
+// The k_mode_x instantiation a launch runs: f(kernel) for the scene and the launch's handoff choice --
+// STATS x HELP x CN x SH x TR, the 32 instantiations of the library.  A scene staged in LDS has no
+// quantised nodes, so it runs the wide-node ones.
 template <typename F>
-void x_dispatch(const DevScene& sc, XVariant var, bool stats, F&& f) {
-    const bool sh = sc.x_max_depth <= 7;
-    if (var.lds)
-        with_bools([&](auto S, auto W, auto H) { f(XTag<S.value, true, W.value, false, H.value, false, false, false>{}); },
-                   stats, var.w4, sh);
-    else
-        with_bools([&](auto S, auto HP, auto C, auto H, auto T) { f(XTag<S.value, false, false, HP.value, H.value, T.value, C.value, false>{}); },
-                   stats, var.help, sc.xcnodes != nullptr, sh, sc.x_tri_only != 0);
-}
-// (k_mode_x's W4 parameter carries XVariant::w4 or XVariant::help: see the kernel's comment)
-template <typename V>
-constexpr auto x_kernel(V) {
-    return &k_mode_x<V::stats, V::lds, V::lds ? V::w4 : V::help, V::cn, V::sh, V::tri>;
+void x_dispatch(const DevScene& sc, bool help, bool stats, F&& f) {
+    with_bools([&](auto S, auto HP, auto C, auto H, auto T) { f(&k_mode_x<S.value, HP.value, C.value, H.value, T.value>); },
+               stats, help, sc.xcnodes != nullptr, sc.x_max_depth <= 7, sc.x_tri_only != 0);
 }
 
 hipError_t x_launch_config(const DevScene& sc, int device, XLaunchCfg& cfg) {
-    const bool lds = sc.x_lds_bytes > 0;
-    cfg.lds_bytes = lds ? (size_t)sc.x_lds_bytes + (sc.x_waves4 ? 256 * 10 * sizeof(double) : 0)
-                        : 16 * 256 * sizeof(int) + 256 * (7 * sizeof(double) + 2 * sizeof(int));
+    const bool lds = sc.x_lds_bytes > 0;   // (gi_wf.hip's kernels; k_mode_x reads every scene from global memory)
+    cfg.lds_bytes = 16 * 256 * sizeof(int) + 256 * (7 * sizeof(double) + 2 * sizeof(int));   // level stack, handoff slots
     cfg.var.lds = lds;
     cfg.var.w4 = lds && sc.x_waves4;
     int cus = 0, per_cu = 0;
     hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
     if (e != hipSuccess) return e;
     // the scene's own instantiation, STATS and handoff off (neither moves the occupancy: DESIGN.md §5)
-    x_dispatch(sc, cfg.var, false, [&](auto V) {
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(x_kernel(V)), 64 * kWavesPerBlock,
+    x_dispatch(sc, false, false, [&](auto kernel) {
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kernel), 64 * kWavesPerBlock,
                                                          cfg.lds_bytes);
     });
     if (e != hipSuccess) return e;
@@ -2453,12 +2324,11 @@ hipError_t launch_render(const DevScene& sc, const XLaunchCfg& xc, const CamDev&
         // blocks of work units
         const XEnv& env = x_env();
         const long long n_slots = m.n_local * (kTile * kTile);
-        // HBM-resident scenes: the shadow-ray handoff build (and spread work groups) for launches of
+        // the shadow-ray handoff build (and spread work groups) for launches of
         // at most 32 samples per resident lane -- their time is the longest paths' latency and lanes
         // run out of work early (C4: 10 per lane; X-soup1000, 169 per lane, is throughput-bound and
         // 25% slower spread)
-        XVariant var = xc.var;
-        var.help = !var.lds && env.help && n_slots * (long long)o.spp <= 32ll * 256ll * (long long)xc.resident;
+        const bool help = env.help && n_slots * (long long)o.spp <= 32ll * 256ll * (long long)xc.resident;
         // up to one lane per (pixel slot, sample): single-sample units can occupy that many lanes
         const long long want = (n_slots * (long long)o.spp / 64 + kWavesPerBlock - 1) / kWavesPerBlock;
         const dim3 pgrid((unsigned)std::max<long long>(1, std::min<long long>(want, xc.resident)));
@@ -2492,7 +2362,7 @@ hipError_t launch_render(const DevScene& sc, const XLaunchCfg& xc, const CamDev&
         const int h8 = sc.x_handle8;
         // schedule flags (XFlag, gi_scene.h): the scene's, the launch's and the maximum run length (log2)
         const int xf = sc.x_flags | (env.run_log2 << XF_RUN_SHIFT) | ((o.flags & GI_FLAG_X_NO_SHADOW) ? XF_NO_SHADOW : 0) |
-                       (env.help ? XF_HANDOFF : 0) | (var.help ? XF_SPREAD : 0) | XF_PIXEL_MAJOR | (env.flat ? 0 : XF_NO_FLAT);
+                       (env.help ? XF_HANDOFF : 0) | (help ? XF_SPREAD : 0) | XF_PIXEL_MAJOR | (env.flat ? 0 : XF_NO_FLAT);
         if (form) {   // gi_wf.hip's forms, timed as one pass
             if (!xs.wcnt || (form == 1 && (!xs.wq[0] || !xs.wq[1] || xs.wcap <= 0))) return hipErrorInvalidValue;
             e = launch_wf(sc, xc.var, xc.wf_lds_bytes, form == 2 ? xc.seg_resident : xc.wf_resident, form, cam, light, w, h, y0,
@@ -2503,8 +2373,8 @@ hipError_t launch_render(const DevScene& sc, const XLaunchCfg& xc, const CamDev&
             return hipGetLastError();
         }
         mark(ev_begin);
-        x_dispatch(sc, var, stats, [&](auto V) {
-            hipLaunchKernelGGL(x_kernel(V), pgrid, block, xc.lds_bytes, stream, sc, cam, light, m, o.spp, o.depth, o.seed, rgb, rgb8, st, wk,
+        x_dispatch(sc, help, stats, [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, pgrid, block, xc.lds_bytes, stream, sc, cam, light, m, o.spp, o.depth, o.seed, rgb, rgb8, st, wk,
                                h8, xf);
         });
         mark(ev_end);

@@ -226,9 +226,9 @@ struct DevScene {
     int32_t x_flags;       // Mode X schedule flags (XFlag): XF_INLINE_SHADOW or 0
     int32_t n_xhot;
     int32_t x_lds_bytes;   // > 0: xwnodes + xhot fit in LDS and are staged there by each workgroup
-    int32_t x_waves4;      // LDS-resident scene with light shading: k_mode_x at 4 waves per SIMD
+    int32_t x_waves4;      // LDS-resident scene with light shading: gi_wf.hip's kernels at 4 waves per SIMD
     int32_t x_tri_only;    // every primitive a triangle, every entity ImpTriangle / ExpQuad / ExpCube /
-                           // ExpBox (the 4-wave kinds): HBM-resident k_mode_x's TRI specialisation
+                           // ExpBox (the 4-wave kinds): k_mode_x's TRI specialisation
     int32_t r_tri_only;    // every entity an ImpTriangle: the Mode R kernels' TRI specialisation
     float root_lo[3], root_hi[3];   // Mode X: union of the root's fp32 child boxes (conservative)
     double x_skip_a, x_skip_b;      // Mode X own-plane leaf skip bound (HostScene, gi_build.cpp)
@@ -311,16 +311,17 @@ enum XFlag : int {
     XF_RUN_SHIFT = 8, XF_RUN_MASK = 7,   // bits 8-10: log2 of the maximum run length (GI_X_MAX_RUN)
 };
 
-// The run-time choices that pick a Mode X kernel instantiation besides the scene's own properties.
+// The run-time choices that pick an instantiation of gi_wf.hip's kernels (k_seg, k_wf_bounce, k_cast, the
+// query KAT) besides the scene's own properties.  k_mode_x reads neither field: it traverses every scene
+// in global memory (gi_kernels.hip x_dispatch).
 struct XVariant {
     bool lds = false;    // the scene is staged in LDS (DevScene::x_lds_bytes > 0)
     bool w4 = false;     // ... and its shading is light: 4 waves per SIMD (DevScene::x_waves4)
-    bool help = false;   // per launch, HBM-resident scenes, k_mode_x: the shadow-ray handoff build
 };
-// A kernel instantiation as a type: what the dispatchers (x_dispatch, wf_dispatch) hand to their callers.
-template <bool STATS, bool LDS, bool W4, bool HELP, bool SH, bool TRI, bool CN, bool FLAT>
+// An instantiation of gi_wf.hip's kernels as a type: what wf_dispatch hands to its callers.
+template <bool STATS, bool LDS, bool W4, bool SH, bool TRI, bool CN, bool FLAT>
 struct XTag {
-    static constexpr bool stats = STATS, lds = LDS, w4 = W4, help = HELP, sh = SH, tri = TRI, cn = CN, flat = FLAT;
+    static constexpr bool stats = STATS, lds = LDS, w4 = W4, sh = SH, tri = TRI, cn = CN, flat = FLAT;
 };
 // f(std::bool_constant<b>...) for run-time booleans b...
 template <bool... Bs, typename F>
@@ -334,11 +335,11 @@ void with_bools(F&& f, bool b, R... r) {
 }
 
 // Mode X launch configuration, computed once per scene when it is created (gi_capi.cpp, on the
-// scene's device): kernel variant, dynamic LDS bytes and the resident persistent grid.
+// scene's device): kernel variant, dynamic LDS bytes and the resident persistent grids.
 struct XLaunchCfg {
-    XVariant var;            // kernel variant (help is set per launch)
-    size_t lds_bytes = 0;    // dynamic LDS per workgroup
-    int resident = 1;        // resident 256-thread workgroups on the device (occupancy x CUs)
+    XVariant var;            // gi_wf.hip's kernels: their variant
+    size_t lds_bytes = 0;    // k_mode_x: dynamic LDS per workgroup (level stack and handoff slots, any scene)
+    int resident = 1;        //   and its resident 256-thread workgroups on the device (occupancy x CUs)
     size_t wf_lds_bytes = 0; // wavefront Mode X (k_wf_bounce, k_seg): dynamic LDS per workgroup
     int wf_resident = 1;     //   and the resident workgroups of k_wf_bounce
     int seg_resident = 1;    //   and of k_seg

@@ -208,9 +208,12 @@ __device__ __forceinline__ int wf_trace(float far_r, NodeP W, HotP H, V3 o, V3 d
 #ifndef GI_XFLAT_UNROLL
 #define GI_XFLAT_UNROLL 4   // Phase A records in flight (their loads overlap the previous records' tests)
 #endif
+#ifndef GI_XFLAT_LDS
+#define GI_XFLAT_LDS 0   // (A/B builds) 1: the flat query reads a copy of its leaf table staged in LDS (wf_stage)
+#endif
 typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
 // record k's eight words from the constant address space: a scalar load at a uniform address
-// (GI_XFLAT_LDS, gi_dev.h: from the table's copy staged in LDS, a broadcast read per record)
+// (GI_XFLAT_LDS: from the table's copy staged in LDS, a broadcast read per record)
 __device__ __forceinline__ u32x8 flat_rec_uniform(const XFlatLeaf* tab, int k) {
 #if GI_XFLAT_LDS
     const int4* q = reinterpret_cast<const int4*>(tab + k);
@@ -355,8 +358,10 @@ struct WFArgs {
     unsigned s0, ns;           // the launch's samples [s0, s0 + ns) of the spp (0, spp; or a progressive pass)
 };
 
-// The scene views of a bounce / segment kernel.  LDS: wide nodes, leaf records, primitives and
-// entities staged in LDS by the workgroup (as k_mode_x does); then the per-lane path slots.
+// The scene views of a bounce / segment kernel.  LDS (sc.x_lds_bytes > 0): the workgroup stages the
+// traversal records (wide nodes, leaf records) and the shading records (primitives, entities) at the
+// start of its dynamic LDS, so neither the traversal nor the shading issues a global load (with
+// GI_XFLAT_LDS the flat leaf table too, after the entities); then the per-lane path slots.
 // HBM-resident scenes: the per-lane level stack (16 x 256 ints), then the path slots.
 struct WFView {
     const XWNode* LW = nullptr;
@@ -368,18 +373,37 @@ struct WFView {
     double* pl = nullptr;   // this lane's L (fields 0-2) and T (3-5), pl[f * 256]
 };
 template <bool LDS>
-__device__ __forceinline__ WFView wf_stage(const DevScene& sc, int4* lds_dyn) {
+__device__ __forceinline__ WFView wf_stage(const DevScene& sc, int4* lds) {
     WFView v;
     v.XP = sc.xprims;
     v.EN = sc.ents;
     v.FT = sc.xflat;
     if constexpr (LDS) {
-        const XStaged s = x_stage_lds<GI_XFLAT_LDS != 0>(sc, lds_dyn);
-        v.LW = s.W; v.LH = s.H; v.XP = s.XP; v.EN = s.EN; v.FT = s.FT;
-        v.pl = reinterpret_cast<double*>(s.end) + threadIdx.x;
+        const int nw = sc.n_xwnodes * (int)(sizeof(XWNode) / sizeof(int4));
+        const int nh = sc.n_xhot * (int)(sizeof(XHot) / sizeof(int4));
+        const int np = sc.n_xprims * (int)(sizeof(XPrim) / sizeof(int4));
+        const int ne = sc.n_ents * (int)(sizeof(REnt) / sizeof(int4));
+        const int nf = GI_XFLAT_LDS ? sc.n_xflat * (int)(sizeof(XFlatLeaf) / sizeof(int4)) : 0;
+        const int4* gw = reinterpret_cast<const int4*>(sc.xwnodes);
+        const int4* gh = reinterpret_cast<const int4*>(sc.xhot);
+        const int4* gp = reinterpret_cast<const int4*>(sc.xprims);
+        const int4* ge = reinterpret_cast<const int4*>(sc.ents);
+        const int4* gf = reinterpret_cast<const int4*>(sc.xflat);
+        for (int i = threadIdx.x; i < nw; i += blockDim.x) lds[i] = gw[i];
+        for (int i = threadIdx.x; i < nh; i += blockDim.x) lds[nw + i] = gh[i];
+        for (int i = threadIdx.x; i < np; i += blockDim.x) lds[nw + nh + i] = gp[i];
+        for (int i = threadIdx.x; i < ne; i += blockDim.x) lds[nw + nh + np + i] = ge[i];
+        for (int i = threadIdx.x; i < nf; i += blockDim.x) lds[nw + nh + np + ne + i] = gf[i];
+        __syncthreads();
+        v.LW = reinterpret_cast<const XWNode*>(lds);
+        v.LH = reinterpret_cast<const XHot*>(lds + nw);
+        v.XP = reinterpret_cast<const XPrim*>(lds + nw + nh);
+        v.EN = reinterpret_cast<const REnt*>(lds + nw + nh + np);
+        if (GI_XFLAT_LDS) v.FT = reinterpret_cast<const XFlatLeaf*>(lds + nw + nh + np + ne);
+        v.pl = reinterpret_cast<double*>(lds + nw + nh + np + ne + nf) + threadIdx.x;
     } else {
-        v.nst = reinterpret_cast<int*>(lds_dyn) + threadIdx.x;   // 16 levels x 256 lanes
-        v.pl = reinterpret_cast<double*>(reinterpret_cast<int*>(lds_dyn) + 16 * 256) + threadIdx.x;
+        v.nst = reinterpret_cast<int*>(lds) + threadIdx.x;   // 16 levels x 256 lanes
+        v.pl = reinterpret_cast<double*>(reinterpret_cast<int*>(lds) + 16 * 256) + threadIdx.x;
     }
     return v;
 }
@@ -989,12 +1013,12 @@ size_t wf_scene_lds_bytes(const DevScene& sc) { return (size_t)sc.x_lds_bytes + 
 template <typename F>
 void wf_dispatch(const DevScene& sc, XVariant var, bool flat, bool stats, F&& f) {
     if (var.lds && flat && sc.x_flat)   // (SH only shapes the tree walk's level masks: one flat kernel per W4)
-        with_bools([&](auto S, auto W) { f(XTag<S.value, true, W.value, false, true, W.value, false, true>{}); }, stats, var.w4);
+        with_bools([&](auto S, auto W) { f(XTag<S.value, true, W.value, true, W.value, false, true>{}); }, stats, var.w4);
     else if (var.lds)
-        with_bools([&](auto S, auto W, auto H) { f(XTag<S.value, true, W.value, false, H.value, W.value, false, false>{}); },
+        with_bools([&](auto S, auto W, auto H) { f(XTag<S.value, true, W.value, H.value, W.value, false, false>{}); },
                    stats, var.w4, sc.x_max_depth <= 7);
     else
-        with_bools([&](auto S, auto T, auto C) { f(XTag<S.value, false, false, false, false, T.value, C.value, false>{}); },
+        with_bools([&](auto S, auto T, auto C) { f(XTag<S.value, false, false, false, T.value, C.value, false>{}); },
                    stats, sc.x_tri_only != 0, sc.xcnodes != nullptr);
 }
 template <typename V>

@@ -119,7 +119,10 @@ typedef enum gi_mode {
 #define GI_FLAG_X_WF 16u         /* Mode X: the wavefront form (one launch per bounce over a compacted queue of
                                     live paths, gi_wf.hip) whatever the scene; same frame bit for bit.  A test
                                     reference (slower everywhere) */
-#define GI_FLAG_X_MEGA 32u       /* Mode X: the persistent path-state kernel (k_mode_x) whatever the scene */
+#define GI_FLAG_X_MEGA 32u       /* Mode X: the persistent path-state kernel (k_mode_x) whatever the scene.  It reads
+                                    every scene from global memory: a scene that k_seg stages in LDS
+                                    (gi_scene_info.x_lds_resident) is traversed there like a large one -- same
+                                    frame bit for bit, slower than the default; for tests and A/B */
 #define GI_FLAG_X_SEG 64u        /* Mode X: the segment-synchronous persistent form (k_seg: every loop
                                     iteration one whole path segment per lane).  None of the three form
                                     flags: chosen per launch (GI_X_WF=0/1/2 overrides) */

@@ -5,8 +5,9 @@
 //    spatial-split BVH of scenes over 8192 primitives: scene 2), every fp32 child box of a BVH
 //    without spatial splits contains its subtree's fp64 primitive bounds, parent pointers consistent,
 //    depth within the 16 mask levels of the traversal;
-//  * traversal: the kernel's stackless front-to-back walk (k_mode_x, restated here step for step:
-//    per-level 8-bit child masks, slot k ^ octant order, re-cull against the current best t)
+//  * traversal: the kernels' stackless front-to-back walk (gi_wf.hip's wf_trace on a scene staged in
+//    LDS, restated here step for step: per-level 8-bit child masks, slot k ^ octant order, parent-pointer
+//    climb, re-cull against the current best t; k_mode_x walks the same masks without the re-cull)
 //    returns the same closest hit (t, primitive) as a brute-force loop over all primitives, for
 //    closest and any-hit (shadow) queries, on random soups and on the Cornell box.
 //   xaccel_check <n_rays>
@@ -125,7 +126,7 @@ static void lvl_set(uint64_t& lo, uint64_t& hi, int l, uint32_t m) {
     else hi = (hi & ~(0xFFull << (8 * (l - 8)))) | ((uint64_t)m << (8 * (l - 8)));
 }
 
-// k_mode_x's traversal of one ray; shadow: any hit with t < tmax
+// wf_trace's traversal of one ray; shadow: any hit with t < tmax
 static long g_prim_tests = 0;
 static int traverse(const HostScene& s, V3 o, V3 d, bool shadow, double tmax, double& tbest, long& visits, int skip = -1) {
     // the device uses v_rcp_f32 (1 ulp) here; the correctly rounded fp32 reciprocal stands in for it
@@ -138,7 +139,7 @@ static int traverse(const HostScene& s, V3 o, V3 d, bool shadow, double tmax, do
     const uint32_t rm = children_mask(&s.xwnodes[0], of, ivf, tbest_f, dmask, skip);
     lvl_set(mlo, mhi, 0, rm);
     bool raying = rm != 0;
-    while (raying) {   // one iteration = one traversal step of k_mode_x
+    while (raying) {   // one iteration = one traversal step of wf_trace
         const uint32_t msk = lvl_get(mlo, mhi, level);
         const int k = __builtin_ctz(msk);
         lvl_set(mlo, mhi, level, msk & (msk - 1));

@@ -273,3 +273,78 @@ def test_mode_x_camera_placements_bit_exact(torch_cuda, scene, cam):
     assert same.all(), f"{scene} {cam}: {int((~same).sum())} of {same.size} pixels differ, first {int(np.flatnonzero(~same)[0])}"
     assert (rgb8 == o["q"]).all()
     assert int(st.cpu().numpy()[gi.STAT_RAYS]) == int(o["ncand"].sum())
+
+
+# ---- k_mode_x forced onto small scenes -----------------------------------------------------------------
+# k_mode_x reads every scene from global memory, so forcing it (GI_FLAG_X_MEGA) onto a scene that k_seg
+# stages in LDS runs the instantiation a large scene of the same properties would: STATS x HELP x CN x
+# SH x TR.  scene -> the properties of the device scene that pick the instantiation (None: not asserted).
+MEGA_W, MEGA_H, MEGA_SPP, MEGA_DEPTH, MEGA_SEED = 48, 40, 3, 5, 2019
+MEGA_SCENES = {
+    "corner3_octree": dict(SH=False, TRI=True, CN=False),   # 12 levels: the two-word level masks
+    "cornell_sphere": dict(SH=True, TRI=False, CN=False),   # a sphere: the general shading and primitive test
+    "one_triangle": dict(SH=True, TRI=True, CN=False),
+    "empty": None,                                          # no primitive: every pixel 0, nothing hangs
+    "soup_xcnode": dict(SH=None, TRI=True, CN=True),        # quantised nodes
+}
+_mega_ref = {}
+
+
+def mega_reference(name):
+    """The oracle's frame of a scene (its own camera), computed once and shared by the two tests."""
+    if name not in _mega_ref:
+        sc = QUERY_SCENES[name][0]()[0]
+        o = U.oracle_render(sc.to_scn(), MEGA_W, MEGA_H, mode=1, spp=MEGA_SPP, depth=MEGA_DEPTH, seed=MEGA_SEED)
+        for a in o.values():
+            if isinstance(a, np.ndarray):
+                a.setflags(write=False)
+        _mega_ref[name] = o
+    return _mega_ref[name]
+
+
+@pytest.mark.parametrize("name", sorted(MEGA_SCENES))
+def test_forced_k_mode_x_on_small_scenes_bit_exact(torch_cuda, name):
+    """GI_FLAG_X_MEGA on scenes k_seg would run (LDS-resident ones, and a small quantised soup): the 48 x
+    40 frame at 3 spp, depth 5 equals the oracle's bit for bit, RGB888 included -- launches this small
+    take the shadow-ray handoff build.  The scenes cover the instantiation axes: a 12-level tree (SH
+    off), a sphere (TR off), quantised nodes (CN on), one triangle, and the empty scene (all 0)."""
+    sc, d = dev_of(name)
+    want = MEGA_SCENES[name]
+    if want is not None:   # the scene still has the properties the case is there for
+        var, info = d.kat_x_variant(0 if want["CN"] else TREE), d.info()
+        assert info["x_node_bytes"] == (128 if want["CN"] else 256), info
+        assert var["CN"] == want["CN"] and var["TRI"] == want["TRI"], var
+        assert want["SH"] is None or var["SH"] == want["SH"], var
+    assert d.x_form(spp=MEGA_SPP, depth=MEGA_DEPTH, flags=gi.FLAG_X_MEGA) == "k_mode_x"
+    o = mega_reference(name)
+    rgb, rgb8 = d.render(gi.Camera(sc.cam_pos, sc.cam_look, sc.focal), sc.light, MEGA_W, MEGA_H, mode=gi.MODE_X,
+                         spp=MEGA_SPP, depth=MEGA_DEPTH, seed=MEGA_SEED, flags=gi.FLAG_X_MEGA)
+    same = U.bits_equal(rgb.reshape(-1, 3), o["rgb"]).all(1)
+    assert same.all(), f"{name}: {int((~same).sum())} of {same.size} pixels differ, first {int(np.flatnonzero(~same)[0])}"
+    assert (rgb8.reshape(-1, 3) == o["q"]).all()
+    if name == "empty":
+        assert not rgb.any() and not rgb8.any()
+    else:
+        assert (o["hit"] >= 0).mean() >= 0.30, name   # the frame sees the scene
+
+
+def test_forced_k_mode_x_on_small_scenes_without_handoff(torch_cuda, tmp_path):
+    """The same frames from the builds without the shadow-ray handoff (GI_X_HELP=0, read once per
+    process: a child process renders all the scenes): equal to the oracle's bit for bit."""
+    import os
+    import subprocess
+    import sys
+    out = tmp_path / "mega_nohelp.npz"
+    code = ("import sys, numpy as np; sys.path.insert(0, %r); sys.path.insert(0, %r); import oracle_util as U; "
+            "from x_scenes import QUERY_SCENES, with_env; gi = U.pkg(); res = {}\n"
+            "for name in %r:\n"
+            "    sc, env = QUERY_SCENES[name][0](); d = with_env(env, lambda: gi.DeviceScene.from_scene(sc))\n"
+            "    res[name] = d.render(gi.Camera(sc.cam_pos, sc.cam_look, sc.focal), sc.light, %d, %d, mode=gi.MODE_X, "
+            "spp=%d, depth=%d, seed=%d, flags=gi.FLAG_X_MEGA)[0]\n"
+            "np.savez(%r, **res)") % (U.ROOT, os.path.join(U.ROOT, "tests"), tuple(sorted(MEGA_SCENES)), MEGA_W, MEGA_H,
+                                      MEGA_SPP, MEGA_DEPTH, MEGA_SEED, str(out))
+    subprocess.run([sys.executable, "-c", code], check=True, timeout=300, env=dict(os.environ, GI_X_HELP="0"))
+    got = np.load(out)
+    for name in sorted(MEGA_SCENES):
+        same = U.bits_equal(got[name].reshape(-1, 3), mega_reference(name)["rgb"]).all(1)
+        assert same.all(), f"{name}: {int((~same).sum())} of {same.size} pixels differ, first {int(np.flatnonzero(~same)[0])}"
