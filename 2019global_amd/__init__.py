@@ -19,7 +19,10 @@ render raises ``GIError``.
 Lower-level handles for benchmarks and multi-GPU: ``DeviceScene`` (a scene resident in HBM) with
 ``render_device`` into caller-owned device buffers on a HIP stream; ``MultiScene`` (several GPUs of
 one process, RCCL gather; ``RayTracer`` uses it when ``GI_DEVICES`` lists more than one device);
-``Octree.intersect`` (the reference's public candidate query, on the host).
+``Octree.intersect`` (the reference's public candidate query, on the host).  ``DeviceScene.intersect`` /
+``occluded`` answer batches of rays; ``DeviceScene.render_aov`` returns a frame's first-hit feature
+buffers (distance, normal, albedo, primitive, entity, texture coordinate) and ``camera_rays`` its pixel
+rays as ray records, each with a ``_device`` form on a HIP stream.
 """
 from __future__ import annotations
 
@@ -37,6 +40,7 @@ __all__ = [
     "ExpSphere", "ExpCube", "ExpCone", "ExpRectangle", "ExpBox",
     "RayTracer", "DeviceScene", "MODE_R", "MODE_X", "STAT_RAYS", "STAT_NODES", "STAT_PRIMS",
     "STAT_PIXELS", "TILE", "MultiScene", "devices_from_env", "obj_entities", "RAY_DOUBLES",
+    "AOV_OUTPUTS", "camera_rays", "camera_rays_device",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -62,8 +66,12 @@ STAT_X_IT_RS, STAT_X_LN_RS, STAT_X_IT_ST, STAT_X_LN_ST = 20, 21, 22, 23
 STAT_R_PAIRS, STAT_R_OVF_TILES = 24, 25
 STATS_N = 26
 TILE = 8
-ABI_VERSION = 12
+ABI_VERSION = 13
 RAY_DOUBLES = 8   # a ray record of the batched queries: o[3], d[3], tmax, reserved (gi.h GI_RAY_DOUBLES)
+# the feature buffers of DeviceScene.render_aov (gi.h gi_aov, in its field order): name -> (dtype, trailing shape)
+AOV_OUTPUTS = ("t", "normal", "albedo", "prim", "entity", "uv")
+_AOV_KINDS = {"t": (np.float64, ()), "normal": (np.float64, (3,)), "albedo": (np.float64, (3,)),
+              "prim": (np.int32, ()), "entity": (np.int32, ()), "uv": (np.int32, (2,))}
 
 
 class GIError(RuntimeError):
@@ -106,6 +114,16 @@ class Hit(ctypes.Structure):
                 ("point", ctypes.c_double * 3), ("normal", ctypes.c_double * 3)]
 
 
+class AovFrame(ctypes.Structure):
+    _fields_ = [("w", ctypes.c_int32), ("h", ctypes.c_int32), ("x0", ctypes.c_int32), ("y0", ctypes.c_int32),
+                ("x1", ctypes.c_int32), ("y1", ctypes.c_int32)]
+
+
+class Aov(ctypes.Structure):
+    _fields_ = [("t", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("albedo", ctypes.c_void_p),
+                ("prim", ctypes.c_void_p), ("entity", ctypes.c_void_p), ("uv", ctypes.c_void_p)]
+
+
 TILE_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint8),
                            ctypes.POINTER(ctypes.c_double))
 
@@ -114,7 +132,7 @@ EXPORTS = ["gi_abi_version", "gi_last_error", "gi_camera_init", "gi_scene_create
            "gi_trace_ray", "gi_kat_expbox", "gi_kat_x_query", "gi_kat_x_variant", "gi_scene_kernel_ms", "gi_scene_x_form", "gi_scene_r_kernel", "gi_octree_create", "gi_octree_destroy",
            "gi_octree_intersect", "gi_multi_create", "gi_multi_destroy", "gi_multi_info", "gi_multi_render", "gi_device_count",
            "gi_device_list", "gi_build_id", "gi_obj_parse", "gi_intersect", "gi_occluded", "gi_intersect_device",
-           "gi_occluded_device"]
+           "gi_occluded_device", "gi_render_aov", "gi_render_aov_device", "gi_camera_rays", "gi_camera_rays_device"]
 
 _lib = None
 _lock = threading.Lock()
@@ -158,6 +176,10 @@ def lib():
         L.gi_occluded.argtypes = [vp, i64, dp, ip]
         L.gi_intersect_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
         L.gi_occluded_device.argtypes = [vp, i64, vp, vp, vp]
+        L.gi_render_aov.argtypes = [vp, ctypes.POINTER(CameraDesc), ctypes.POINTER(AovFrame), ctypes.POINTER(Aov)]
+        L.gi_render_aov_device.argtypes = [vp, ctypes.POINTER(CameraDesc), ctypes.POINTER(AovFrame), ctypes.POINTER(Aov), vp]
+        L.gi_camera_rays.argtypes = [ctypes.POINTER(CameraDesc), ctypes.POINTER(AovFrame), dp]
+        L.gi_camera_rays_device.argtypes = [ctypes.POINTER(CameraDesc), ctypes.POINTER(AovFrame), vp, vp]
         L.gi_scene_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)]
         L.gi_scene_x_form.argtypes = [vp, ctypes.POINTER(Opts), ctypes.POINTER(ctypes.c_int32)]
         L.gi_scene_r_kernel.argtypes = [vp, ctypes.POINTER(Opts), ctypes.POINTER(ctypes.c_int32)]
@@ -200,6 +222,25 @@ def _check_rays(rays) -> int:
             not rays.flags.c_contiguous:
         raise ValueError(f"rays: a C-contiguous float64 array of shape (n, {RAY_DOUBLES}) -- o[3], d[3], tmax, reserved")
     return int(rays.shape[0])
+
+
+def _aov_frame(w, h, window) -> AovFrame:
+    """The gi_aov_frame of a w x h frame and its window (x0, y0, x1, y1), None: the whole frame.  ValueError
+    unless w, h > 0 and 0 <= x0 <= x1 <= w, 0 <= y0 <= y1 <= h (an empty window is allowed).  Checked
+    before the library is touched."""
+    def whole(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+    if not (whole(w) and whole(h)) or w <= 0 or h <= 0 or w >= 2 ** 31 or h >= 2 ** 31:
+        raise ValueError("frame: w and h are positive integers")
+    if window is None:
+        window = (0, 0, w, h)
+    window = tuple(window)
+    if len(window) != 4 or not all(whole(v) for v in window):
+        raise ValueError("window: four integers (x0, y0, x1, y1)")
+    x0, y0, x1, y1 = (int(v) for v in window)
+    if not (0 <= x0 <= x1 <= w and 0 <= y0 <= y1 <= h):
+        raise ValueError(f"window {window}: reversed or not inside the {w} x {h} frame")
+    return AovFrame(int(w), int(h), x0, y0, x1, y1)
 
 
 def _d3(v) -> ctypes.Array:
@@ -585,6 +626,32 @@ class DeviceScene:
         _check(lib().gi_occluded_device(self._h, int(n), d_rays or None, d_occluded or None, stream or None),
                "gi_occluded_device")
 
+    # ---- first-hit feature buffers (gi.h "feature buffers") ------------------------------------------
+    def render_aov(self, cam: "Camera", w: int, h: int, window=None, want=AOV_OUTPUTS) -> dict:
+        """What each pixel of the window (x0, y0, x1, y1) of a w x h frame shows (gi_render_aov; None: the
+        whole frame): the outputs named in want as arrays shaped (rows, cols[, 3 | 2]) -- "t" float64
+        (distance from the camera; inf: no hit), "normal" and "albedo" float64 x 3, "prim" and "entity"
+        int32 (-1: no hit), "uv" int32 x 2.  ValueError for an unknown, repeated or empty want and a
+        window that is reversed or not inside the frame."""
+        want = tuple(want)
+        if not want or any(k not in AOV_OUTPUTS for k in want) or len(set(want)) != len(want):
+            raise ValueError(f"render_aov: want is a non-empty selection of {AOV_OUTPUTS}")
+        f = _aov_frame(w, h, window)
+        rows, cols = f.y1 - f.y0, f.x1 - f.x0
+        bufs = {k: np.empty((rows, cols) + _AOV_KINDS[k][1], _AOV_KINDS[k][0]) for k in want}
+        a = Aov(**{k: bufs[k].ctypes.data if bufs[k].size else _scratch_ptr() for k in want})
+        _check(lib().gi_render_aov(self._h, ctypes.byref(cam._c), ctypes.byref(f), ctypes.byref(a)), "gi_render_aov")
+        return bufs
+
+    def render_aov_device(self, cam: "Camera", w: int, h: int, window=None, d_t: int = 0, d_normal: int = 0,
+                          d_albedo: int = 0, d_prim: int = 0, d_entity: int = 0, d_uv: int = 0, stream: int = 0) -> None:
+        """Asynchronous feature buffers into device planes (gi_render_aov_device); pointers are ints, an
+        output of 0 is not written."""
+        f = _aov_frame(w, h, window)
+        a = Aov(d_t or None, d_normal or None, d_albedo or None, d_prim or None, d_entity or None, d_uv or None)
+        _check(lib().gi_render_aov_device(self._h, ctypes.byref(cam._c), ctypes.byref(f), ctypes.byref(a), stream or None),
+               "gi_render_aov_device")
+
     def kat_x_variant(self, flags: int = 0) -> dict:
         """The kernel variant kat_x_query runs with these flags (flags 0: k_seg's for this scene):
         {"LDS", "W4", "SH", "TRI", "CN", "FLAT"} -> bool (gi_kat_x_variant)."""
@@ -610,6 +677,38 @@ class DeviceScene:
                                     out["skip2"].ctypes.data_as(ip), ctypes.byref(sc)), "gi_kat_x_query")
         out["skip_cos"] = sc.value if n else None
         return out
+
+
+_scratch = None
+
+
+def _scratch_ptr() -> int:
+    """A valid non-null host address for an output of zero elements (an empty window)."""
+    global _scratch
+    if _scratch is None:
+        _scratch = np.zeros(8)
+    return _scratch.ctypes.data
+
+
+def camera_rays(cam: "Camera", w: int, h: int, window=None) -> np.ndarray:
+    """The pixel rays of the window (x0, y0, x1, y1) of a w x h frame (None: the whole frame) as ray
+    records for DeviceScene.intersect / occluded (gi_camera_rays): (rows * cols, RAY_DOUBLES) float64,
+    row-major over the window -- o = the camera position, d the normalised primary direction the renders
+    and render_aov trace, tmax = inf, reserved = 0."""
+    f = _aov_frame(w, h, window)
+    rays = np.empty(((f.y1 - f.y0) * (f.x1 - f.x0), RAY_DOUBLES), np.float64)
+    p = rays.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if rays.size else \
+        ctypes.cast(_scratch_ptr(), ctypes.POINTER(ctypes.c_double))
+    _check(lib().gi_camera_rays(ctypes.byref(cam._c), ctypes.byref(f), p), "gi_camera_rays")
+    return rays
+
+
+def camera_rays_device(cam: "Camera", w: int, h: int, d_rays: int, window=None, stream: int = 0) -> None:
+    """Asynchronous camera_rays into a device buffer of rows * cols records, 16-byte aligned, on the current
+    device (gi_camera_rays_device); the pointer is an int."""
+    f = _aov_frame(w, h, window)
+    _check(lib().gi_camera_rays_device(ctypes.byref(cam._c), ctypes.byref(f), d_rays or None, stream or None),
+           "gi_camera_rays_device")
 
 
 def devices_from_env(default=None):

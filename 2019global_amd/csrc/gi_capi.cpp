@@ -41,6 +41,8 @@ hipError_t launch_x_query(const DevScene& sc, const XLaunchCfg& xc, V3 cam_pos, 
                           int32_t* oi, double* od, hipStream_t stream);
 void x_query_variant(const DevScene& sc, const XLaunchCfg& xc, int flags, int32_t out[6]);
 hipError_t launch_ray_query(const DevScene& sc, const XLaunchCfg& xc, bool any, const CastIO& io, hipStream_t stream);
+hipError_t launch_aov(const DevScene& sc, const XLaunchCfg& xc, const CamDev& cam, const AovIO& io, hipStream_t stream);
+hipError_t launch_cam_rays(const CamDev& cam, int x0, int y0, int cols, int rows, double* rays, hipStream_t stream);
 }  // namespace gi
 
 using namespace gi;
@@ -926,6 +928,111 @@ int gi_occluded(gi_scene* s, int64_t n, const double* rays, int32_t* occluded) {
         if (rc) return rc;
         e = hipMemcpy(occluded, dc.p, m * sizeof(int32_t), hipMemcpyDeviceToHost);
         return e == hipSuccess ? GI_OK : hip_fail(e, "gi_occluded");
+    });
+}
+
+// ---- first-hit feature buffers and camera rays (gi.h "feature buffers"; gi_wf.hip k_aov, k_cam_rays) ----
+// Like the ray queries: the scene's immutable records and launch configuration only, no lock, no
+// ordering against the scene's renders, nothing of the progressive-frame state is touched.
+namespace {
+// the frame, its window and the camera of an AOV / camera-ray call; *empty: the window holds no pixel
+int check_aov_frame(const gi_camera* cam, const gi_aov_frame* f, bool* empty) {
+    if (!cam || !f) return fail(GI_ERR_ARG, "null camera or frame");
+    if (f->w <= 0 || f->h <= 0 || (int64_t)f->w * f->h > (int64_t)1 << 34) return fail(GI_ERR_ARG, "bad frame size");
+    if (f->x0 < 0 || f->y0 < 0 || f->x1 > f->w || f->y1 > f->h || f->x0 > f->x1 || f->y0 > f->y1)
+        return fail(GI_ERR_ARG, "the window [x0, x1) x [y0, y1) is reversed or not inside the frame");
+    bool fin = std::isfinite(cam->focal);
+    for (int k = 0; k < 3; ++k) fin = fin && std::isfinite(cam->pos[k]) && std::isfinite(cam->up[k]) && std::isfinite(cam->forward[k]);
+    if (!fin) return fail(GI_ERR_ARG, "non-finite camera field");
+    *empty = f->x0 == f->x1 || f->y0 == f->y1;
+    return GI_OK;
+}
+bool aov_all_null(const gi_aov& a) { return !a.t && !a.normal && !a.albedo && !a.prim && !a.entity && !a.uv; }
+AovIO aov_io(const gi_aov_frame& f, const gi_aov& a) {
+    return AovIO{f.x0, f.y0, f.x1 - f.x0, f.y1 - f.y0, a.t, a.normal, a.albedo, a.prim, a.entity, a.uv};
+}
+}  // namespace
+
+int gi_render_aov_device(gi_scene* s, const gi_camera* cam, const gi_aov_frame* frame, const gi_aov* d_out, void* stream) {
+    return guard([&]() -> int {
+        DeviceRestore keep;   // the caller's current device, restored on return
+        if (!s) return fail(GI_ERR_ARG, "null scene");
+        if (!d_out) return fail(GI_ERR_ARG, "null output struct");
+        bool empty = false;
+        int rc = check_aov_frame(cam, frame, &empty);
+        if (rc) return rc;
+        if (aov_all_null(*d_out)) return fail(GI_ERR_ARG, "gi_render_aov: every output is null");
+        if (empty) return GI_OK;
+        if ((rc = bind_device(s->device))) return rc;
+        const hipError_t e = launch_aov(s->dev, s->xcfg, make_cam(*cam, frame->w), aov_io(*frame, *d_out), static_cast<hipStream_t>(stream));
+        return e == hipSuccess ? GI_OK : hip_fail(e, "gi_render_aov launch");
+    });
+}
+
+int gi_render_aov(gi_scene* s, const gi_camera* cam, const gi_aov_frame* frame, const gi_aov* out) {
+    return guard([&]() -> int {
+        DeviceRestore keep;   // the caller's current device, restored on return
+        if (!s) return fail(GI_ERR_ARG, "null scene");
+        if (!out) return fail(GI_ERR_ARG, "null output struct");
+        bool empty = false;
+        int rc = check_aov_frame(cam, frame, &empty);
+        if (rc) return rc;
+        if (aov_all_null(*out)) return fail(GI_ERR_ARG, "gi_render_aov: every output is null");
+        if (empty) return GI_OK;
+        if ((rc = bind_device(s->device))) return rc;
+        const size_t m = (size_t)(frame->x1 - frame->x0) * (size_t)(frame->y1 - frame->y0);
+        DevBuf dt, dn, da, dp, de, du;
+        hipError_t e = hipSuccess;
+        if (out->t) e = dt.alloc(m * sizeof(double));
+        if (e == hipSuccess && out->normal) e = dn.alloc(m * 3 * sizeof(double));
+        if (e == hipSuccess && out->albedo) e = da.alloc(m * 3 * sizeof(double));
+        if (e == hipSuccess && out->prim) e = dp.alloc(m * sizeof(int32_t));
+        if (e == hipSuccess && out->entity) e = de.alloc(m * sizeof(int32_t));
+        if (e == hipSuccess && out->uv) e = du.alloc(m * 2 * sizeof(int32_t));
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc (feature buffer staging)");
+        const gi_aov d{static_cast<double*>(dt.p), static_cast<double*>(dn.p), static_cast<double*>(da.p),
+                       static_cast<int32_t*>(dp.p), static_cast<int32_t*>(de.p), static_cast<int32_t*>(du.p)};
+        e = launch_aov(s->dev, s->xcfg, make_cam(*cam, frame->w), aov_io(*frame, d), nullptr);
+        if (e != hipSuccess) return hip_fail(e, "gi_render_aov launch");
+        if (out->t) e = hipMemcpy(out->t, dt.p, m * sizeof(double), hipMemcpyDeviceToHost);   // (synchronous copies on the launch's stream)
+        if (e == hipSuccess && out->normal) e = hipMemcpy(out->normal, dn.p, m * 3 * sizeof(double), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && out->albedo) e = hipMemcpy(out->albedo, da.p, m * 3 * sizeof(double), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && out->prim) e = hipMemcpy(out->prim, dp.p, m * sizeof(int32_t), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && out->entity) e = hipMemcpy(out->entity, de.p, m * sizeof(int32_t), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && out->uv) e = hipMemcpy(out->uv, du.p, m * 2 * sizeof(int32_t), hipMemcpyDeviceToHost);
+        return e == hipSuccess ? GI_OK : hip_fail(e, "gi_render_aov");
+    });
+}
+
+int gi_camera_rays_device(const gi_camera* cam, const gi_aov_frame* frame, double* d_rays, void* stream) {
+    return guard([&]() -> int {
+        bool empty = false;
+        int rc = check_aov_frame(cam, frame, &empty);
+        if (rc) return rc;
+        if (!d_rays) return fail(GI_ERR_ARG, "null rays");
+        if (reinterpret_cast<uintptr_t>(d_rays) & 15) return fail(GI_ERR_ARG, "device ray records must be 16-byte aligned");
+        if (empty) return GI_OK;
+        const hipError_t e = launch_cam_rays(make_cam(*cam, frame->w), frame->x0, frame->y0, frame->x1 - frame->x0,
+                                             frame->y1 - frame->y0, d_rays, static_cast<hipStream_t>(stream));
+        return e == hipSuccess ? GI_OK : hip_fail(e, "gi_camera_rays launch");
+    });
+}
+
+int gi_camera_rays(const gi_camera* cam, const gi_aov_frame* frame, double* rays) {
+    return guard([&]() -> int {
+        bool empty = false;
+        int rc = check_aov_frame(cam, frame, &empty);
+        if (rc) return rc;
+        if (!rays) return fail(GI_ERR_ARG, "null rays");
+        if (empty) return GI_OK;
+        const size_t bytes = (size_t)(frame->x1 - frame->x0) * (size_t)(frame->y1 - frame->y0) * GI_RAY_DOUBLES * sizeof(double);
+        DevBuf dr;
+        hipError_t e = dr.alloc(bytes);
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc (camera ray staging)");
+        e = launch_cam_rays(make_cam(*cam, frame->w), frame->x0, frame->y0, frame->x1 - frame->x0, frame->y1 - frame->y0,
+                            static_cast<double*>(dr.p), nullptr);
+        if (e == hipSuccess) e = hipMemcpy(rays, dr.p, bytes, hipMemcpyDeviceToHost);
+        return e == hipSuccess ? GI_OK : hip_fail(e, "gi_camera_rays");
     });
 }
 

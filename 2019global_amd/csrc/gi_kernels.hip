@@ -2260,6 +2260,9 @@ hipError_t x_launch_config(const DevScene& sc, int device, XLaunchCfg& cfg) {
     e = wf_occupancy(sc, cfg.var, flat, cfg.wf_lds_bytes, 4, &per_cu);
     if (e != hipSuccess) return e;
     cfg.occl_resident = std::max(1, cus) * std::max(1, per_cu);
+    e = wf_occupancy(sc, cfg.var, flat, cfg.wf_lds_bytes, 5, &per_cu);   // the feature buffers (k_aov)
+    if (e != hipSuccess) return e;
+    cfg.aov_resident = std::max(1, cus) * std::max(1, per_cu);
     return hipSuccess;
 }
 
@@ -2434,6 +2437,14 @@ hipError_t launch_cast(const DevScene& sc, XVariant var, bool flat, size_t lds_b
 hipError_t launch_ray_query(const DevScene& sc, const XLaunchCfg& xc, bool any, const CastIO& io, hipStream_t stream) {
     const XQueryCfg c = x_query_cfg(xc, 0);
     return launch_cast(sc, c.var, c.flat, c.lds_bytes, any ? xc.occl_resident : xc.cast_resident, any, io, stream);
+}
+
+// gi_render_aov*: k_aov in the variant, the flat choice and the dynamic LDS of a k_seg launch on this scene
+hipError_t launch_aov_kernel(const DevScene& sc, XVariant var, bool flat, size_t lds_bytes, int resident, const CamDev& cam,
+                             const AovIO& io, hipStream_t stream);
+hipError_t launch_aov(const DevScene& sc, const XLaunchCfg& xc, const CamDev& cam, const AovIO& io, hipStream_t stream) {
+    const XQueryCfg c = x_query_cfg(xc, 0);
+    return launch_aov_kernel(sc, c.var, c.flat, c.lds_bytes, xc.aov_resident, cam, io, stream);
 }
 
 hipError_t launch_trace_ray(const DevScene& sc, V3 o, V3 d, V3 light, int32_t* out_i, double* out_d, hipStream_t stream) {

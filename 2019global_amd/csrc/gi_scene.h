@@ -345,6 +345,7 @@ struct XLaunchCfg {
     int seg_resident = 1;    //   and of k_seg
     int cast_resident = 1;   // the ray queries (k_cast, gi_wf.hip): closest hit
     int occl_resident = 1;   //   and any hit
+    int aov_resident = 1;    // the feature buffers (k_aov, gi_wf.hip)
 };
 
 // One call of the public ray queries (gi_intersect*, gi_occluded*; gi_wf.hip k_cast): device pointers.
@@ -356,6 +357,19 @@ struct CastIO {
     int32_t* ent;
     double* nrm;
     int32_t* occl;        // any hit: 1 / 0
+};
+
+// One call of the feature buffers (gi_render_aov*; gi_wf.hip k_aov): the window [x0, x0 + cols) x
+// [y0, y0 + rows) of the frame and its output planes, device pointers, row-major over the window;
+// a null pointer: that plane is not written.
+struct AovIO {
+    int x0, y0, cols, rows;
+    double* t;            // distance from the camera position (+inf: no hit)
+    double* nrm;          // facing unit normal (3 per pixel)
+    double* alb;          // the hit's texel (3 per pixel)
+    int32_t* prim;        // Mode X primitive, entity (-1: no hit)
+    int32_t* ent;
+    int32_t* uv;          // texture coordinate (2 per pixel)
 };
 
 }  // namespace gi

@@ -998,6 +998,120 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
     }
 }
 
+// Lane-to-pixel mapping of the feature-buffer kernels: batch b (64 lanes) of a cols x rows window takes
+// the 64 consecutive window pixels 64 b .. 64 b + 63 in row order, so every plane store of a wave is one
+// contiguous run (512 B of t, 1536 B of normals, ...).  The alternative, 8 x 8 tiles as the renders map
+// their lanes (more coherent rays, stores in row pieces of 8 pixels), was built and measured on the
+// MI355X on a 2048 x 2048 frame, t / prim / entity / normal (DESIGN.md §9 "Feature buffers";
+// profiles/aov_rate.jsonl): the Cornell box 0.095-0.098 ms by rows, 0.094-0.095 by tiles (ranges
+// overlap); soup100000 0.713 by rows against 0.739 ms.  Rows stayed, the tile mapping was removed.
+__host__ __device__ inline long long aov_batches(int cols, int rows) { return ((long long)cols * (long long)rows + 63) / 64; }
+// window pixel (px, py) of a lane; false: the lane has no pixel.  The division in 32 bits where it
+// suffices (a frame holds at most 2^34 pixels, gi_capi.cpp check_aov_frame)
+__device__ __forceinline__ bool aov_pixel(int cols, int rows, long long b, int lane, int& px, int& py) {
+    const long long i = 64 * b + lane;
+    if (i < (1ll << 32)) {
+        const unsigned q = (unsigned)i / (unsigned)cols;
+        py = (int)q;
+        px = (int)((unsigned)i - q * (unsigned)cols);
+    } else {
+        const long long q = i / (long long)cols;
+        py = (int)q;
+        px = (int)(i - q * (long long)cols);
+    }
+    return i < (long long)cols * (long long)rows;
+}
+
+// First-hit feature buffers (gi_render_aov*; DESIGN.md §5 "Feature buffers"): what each pixel of the
+// window [x0, x0 + cols) x [y0, y0 + rows) of a frame shows.  One lane per pixel; the pixel's ray is
+// the primary ray of a 1-spp Mode X frame by k_seg's own steps -- o = cam.pos, d =
+// normalize(primary_dir(x, y)) without jitter, the root pretest (wf_primary_misses: a miss), the
+// launch-uniform far-camera rule (ray_far_r), no skip group -- and its closest hit x_query's in the
+// variant a k_seg launch on the scene runs, the scene staged as k_seg stages it.  The hit's facing
+// normal, entity, texture coordinate and texel are x_segment's.  Outputs are row-major planes over the
+// window (64-bit indices); a null plane is not written.  Persistent grid, static schedule (as k_cast):
+// no device counter, none of the scene's render scratch is read or written.
+// Resources (hipcc -S, gfx950): DESIGN.md §9 "Feature buffers".
+template <bool LDS, bool W4, bool SH, bool TRI, bool CN, bool FLAT>
+__global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_WAVES) void k_aov(DevScene sc, CamDev cam, AovIO io) {
+    extern __shared__ int4 lds_dyn[];
+    const WFView v = wf_stage<LDS>(sc, lds_dyn);
+    const int lane = threadIdx.x & 63;
+    const float far_r = ray_far_r(sc, cam.pos);   // (far cameras: gi_dev.h ray_org32)
+    const long long n_batches = aov_batches(io.cols, io.rows);
+    const long long stride = (long long)gridDim.x * (long long)(blockDim.x >> 6);
+    const bool want_tex = io.alb || io.uv;
+    for (long long b = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); b < n_batches; b += stride) {
+        int px = 0, py = 0;
+        const bool in = aov_pixel(io.cols, io.rows, b, lane, px, py);
+        const V3 o = cam.pos;
+        V3 d = v3(1, 0, 0);
+        bool act = false;
+        if (in) {
+            const V3 d0 = primary_dir(cam, (double)(io.x0 + px), (double)(io.y0 + py));
+            if (!wf_primary_misses(sc, cam, d0)) {
+                act = true;
+                d = normalize(d0);
+            }
+        }
+        uint32_t nnode = 0, nprim = 0, nsteps = 0;
+        double tb = INFINITY;
+        const int best = x_query<false, LDS, SH, TRI, CN, FLAT>(sc, v, far_r, o, d, INFINITY, act, tb, nnode, nprim, nsteps, 254);
+        const bool hit = act && best >= 0;
+        if (in) {
+            const long long i = (long long)py * (long long)io.cols + (long long)px;
+            int ent = -1, tu = 0, tv = 0;
+            V3 N = v3(0, 0, 0), tc = v3(0, 0, 0);
+            if (hit) {   // x_segment's facing normal, texture coordinate and texel
+                const XPrim& p = v.XP[best];
+                ent = p.ent;
+                const V3 P = o + tb * d;
+                N = (TRI || p.kind == 0) ? ld3(p.n) : normalize(P - ld3(p.a));
+                N = dot(d, N) < 0 ? N : -N;
+                if (want_tex) {
+                    const REnt& e = v.EN[p.ent];
+                    x_texcoord<TRI>(sc, e, P, tu, tv);
+                    tc = texel(ld3(e.color), tu, tv);
+                }
+            }
+            if (io.t) io.t[i] = hit ? tb : INFINITY;
+            if (io.prim) io.prim[i] = hit ? best : -1;
+            if (io.ent) io.ent[i] = ent;
+            if (io.nrm) {
+                double* q = io.nrm + 3 * i;
+                q[0] = N.x; q[1] = N.y; q[2] = N.z;
+            }
+            if (io.alb) {
+                double* q = io.alb + 3 * i;
+                q[0] = tc.x; q[1] = tc.y; q[2] = tc.z;
+            }
+            if (io.uv) {   // (two 4-byte stores: the caller's plane need not be 8-byte aligned)
+                int32_t* q = io.uv + 2 * i;
+                q[0] = tu; q[1] = tv;
+            }
+        }
+    }
+}
+
+// The window's pixel rays as records of the ray queries (gi_camera_rays*): o = cam.pos, d = k_aov's
+// normalize(primary_dir(x, y)) bit for bit, tmax = +inf, reserved = 0; row-major over the window,
+// one lane per pixel, a 64-byte record in four 16-byte stores.  No scene.
+__global__ __launch_bounds__(256) void k_cam_rays(CamDev cam, int x0, int y0, int cols, int rows, double* rays) {
+    const long long n_batches = aov_batches(cols, rows);
+    const long long stride = (long long)gridDim.x * (long long)(blockDim.x >> 6);
+    const int lane = threadIdx.x & 63;
+    for (long long b = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); b < n_batches; b += stride) {
+        int px = 0, py = 0;
+        if (!aov_pixel(cols, rows, b, lane, px, py)) continue;
+        const V3 d = normalize(primary_dir(cam, (double)(x0 + px), (double)(y0 + py)));
+        double2* q = reinterpret_cast<double2*>(rays) + 4 * (64 * b + lane);
+        q[0] = make_double2(cam.pos.x, cam.pos.y);
+        q[1] = make_double2(cam.pos.z, d.x);
+        q[2] = make_double2(d.y, d.z);
+        q[3] = make_double2(INFINITY, 0.0);
+    }
+}
+
 }  // namespace
 
 // dynamic LDS of the bounce kernel beyond the scene / level stack: the per-lane path slots
@@ -1029,12 +1143,16 @@ constexpr auto bounce_kernel(V) { return &k_wf_bounce<V::stats, V::lds, V::w4, V
 template <bool ANY, typename V>
 constexpr auto cast_kernel(V) { return &k_cast<ANY, V::lds, V::w4, V::sh, V::tri, V::cn, V::flat>; }
 
+template <typename V>
+constexpr auto aov_kernel(V) { return &k_aov<V::lds, V::w4, V::sh, V::tri, V::cn, V::flat>; }
+
 // resident workgroups per CU of the kernel a form (1: k_wf_bounce, 2: k_seg; the ray queries: 3 k_cast
-// closest hit, 4 k_cast any hit) runs for this scene
+// closest hit, 4 k_cast any hit; 5: the feature buffers, k_aov) runs for this scene
 hipError_t wf_occupancy(const DevScene& sc, XVariant var, bool flat, size_t lds_bytes, int form, int* per_cu) {
     hipError_t e = hipSuccess;
     wf_dispatch(sc, var, flat, false, [&](auto V) {
-        const void* f = form == 4   ? reinterpret_cast<const void*>(cast_kernel<true>(V))
+        const void* f = form == 5   ? reinterpret_cast<const void*>(aov_kernel(V))
+                        : form == 4 ? reinterpret_cast<const void*>(cast_kernel<true>(V))
                         : form == 3 ? reinterpret_cast<const void*>(cast_kernel<false>(V))
                         : form == 2 ? reinterpret_cast<const void*>(seg_kernel(V))
                                     : reinterpret_cast<const void*>(bounce_kernel(V));
@@ -1133,6 +1251,30 @@ hipError_t launch_cast(const DevScene& sc, XVariant var, bool flat, size_t lds_b
         if (any) hipLaunchKernelGGL(cast_kernel<true>(V), grid, block, lds_bytes, stream, sc, io);
         else hipLaunchKernelGGL(cast_kernel<false>(V), grid, block, lds_bytes, stream, sc, io);
     });
+    return hipGetLastError();
+}
+
+// The feature buffers' launch: k_aov in k_seg's variant for the scene (wf_dispatch) over a persistent grid
+// of at most `resident` workgroups (wf_occupancy form 5), fewer when the window needs fewer.
+// Asynchronous on `stream`; no allocation, no copy, no synchronisation.
+hipError_t launch_aov_kernel(const DevScene& sc, XVariant var, bool flat, size_t lds_bytes, int resident, const CamDev& cam,
+                             const AovIO& io, hipStream_t stream) {
+    if (io.cols <= 0 || io.rows <= 0) return hipSuccess;
+    const long long want = (aov_batches(io.cols, io.rows) + 3) / 4;   // four waves (batches) per workgroup
+    const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>(want, resident))), block(256);
+    wf_dispatch(sc, var, flat, false, [&](auto V) {
+        hipLaunchKernelGGL(aov_kernel(V), grid, block, lds_bytes, stream, sc, cam, io);
+    });
+    return hipGetLastError();
+}
+
+// gi_camera_rays*: the window's pixel rays as ray records (k_cam_rays), grid-stride over at most 2048
+// workgroups.  Asynchronous on `stream`.
+hipError_t launch_cam_rays(const CamDev& cam, int x0, int y0, int cols, int rows, double* rays, hipStream_t stream) {
+    if (cols <= 0 || rows <= 0) return hipSuccess;
+    const long long want = ((long long)cols * (long long)rows + 255) / 256;
+    const dim3 grid((unsigned)std::min<long long>(want, 2048)), block(256);
+    hipLaunchKernelGGL(k_cam_rays, grid, block, 0, stream, cam, x0, y0, cols, rows, rays);
     return hipGetLastError();
 }
 

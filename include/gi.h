@@ -18,6 +18,10 @@
  *   gi_intersect*        batched ray queries over the Mode X acceleration structure (no reference
  *   gi_occluded*         counterpart): closest hit / any hit of caller-supplied rays, from host buffers
  *                        or device-resident on a HIP stream
+ *   gi_render_aov*       first-hit feature buffers (AOVs) of a frame's pixels: distance, facing normal,
+ *                        albedo, primitive, entity, texture coordinate (no reference counterpart)
+ *   gi_camera_rays*      a frame's pixel rays (raytracer.h:41-43) as ray records for gi_intersect* /
+ *                        gi_occluded*
  *   gi_unshard_device    reassembles a frame from per-rank packed tiles after the RCCL gather
  *   gi_scene_kernel_ms   HIP-event duration of the last timed render's dominant kernel (bench)
  *   gi_scene_x_form      which Mode X form (persistent kernel / wavefront) a render would run
@@ -48,7 +52,7 @@
 extern "C" {
 #endif
 
-#define GI_ABI_VERSION 12
+#define GI_ABI_VERSION 13
 
 typedef enum gi_status {
     GI_OK = 0,
@@ -307,6 +311,58 @@ int gi_occluded_device(gi_scene* scene, int64_t n, const double* d_rays, int32_t
 int gi_intersect(gi_scene* scene, int64_t n, const double* rays, double* t, int32_t* prim, int32_t* entity,
                  double* normal);
 int gi_occluded(gi_scene* scene, int64_t n, const double* rays, int32_t* occluded);
+
+/* ---- first-hit feature buffers (AOVs) and camera rays (ABI 13) ----------------------------------
+ * What does this pixel show?  For every pixel of the window [x0, x1) x [y0, y1) of a w x h frame, the
+ * first surface its primary ray meets, answered by the kernel variant a Mode X render of the scene runs
+ * (gi_kat_x_variant(scene, 0, ...) describes it).
+ *
+ * The pixel's ray is the primary ray of a 1-spp Mode X frame, formed by the functions the render
+ * kernels use: o = cam.pos, d = normalize(top_left - left*x*res - up*y*res) (raytracer.h:41-43) at the
+ * pixel's integer (x, y), without jitter.  The closest hit is the (t, primitive) minimum over t > 1e-7,
+ * ties to the lower primitive index -- gi_intersect's answer for that ray with tmax = +inf.
+ *
+ * gi_aov: one device (gi_render_aov_device) or host (gi_render_aov) pointer per output, each a
+ * row-major plane over the window (rows = y1 - y0, cols = x1 - x0; pixel (x, y) at index
+ * (y - y0) * cols + (x - x0)):
+ *   t        rows*cols fp64: the distance along the unit d, i.e. the Euclidean distance from the
+ *            camera position; +inf without a hit.
+ *   normal   rows*cols*3 fp64: the unit geometric normal at the hit, flipped to face the ray
+ *            (dot(d, normal) < 0) -- the normal Mode X shades with, gi_intersect's; (0, 0, 0) without
+ *            a hit.
+ *   albedo   rows*cols*3 fp64: the texel of the hit entity's material colour at (u, v) (the
+ *            reference's 32 x 32 checker pattern, material.h:48-62) -- the colour Mode X shades with
+ *            and multiplies a diffuse path's throughput by (T *= albedo / 2); (0, 0, 0) without a hit.
+ *   prim     rows*cols int32: Mode X's primitive index, as gi_intersect numbers them; -1 without a hit.
+ *   entity   rows*cols int32: that primitive's entity (push order); -1 without a hit.
+ *   uv       rows*cols*2 int32: the entity's getTextureCoord at the hit point P = o + t d, as Mode X
+ *            computes it; (0, 0) without a hit.
+ *   Outputs    any pointer may be NULL and is then not written; all six NULL is GI_ERR_ARG.
+ *   Arguments  GI_ERR_ARG for a NULL scene, camera, frame or gi_aov; for w <= 0 or h <= 0 (or more
+ *              than 2^34 pixels); for a window that is reversed (x0 > x1, y0 > y1) or not inside the
+ *              frame; for a camera with a non-finite field.  An empty window (x0 == x1 or y0 == y1)
+ *              launches nothing and returns GI_OK.
+ * gi_camera_rays*: the same window's pixel rays as GI_RAY_DOUBLES records, row-major over the window:
+ * o, the same normalised d bit for bit, tmax = +inf, reserved = 0 -- ready for gi_intersect_device /
+ * gi_occluded_device (gi_intersect over them returns the t, prim, entity and normal planes above).  No
+ * scene: they run on the current HIP device.  A NULL ray buffer is GI_ERR_ARG; device ray records are
+ * 16-byte aligned (GI_ERR_ARG otherwise).
+ * The _device variants take device pointers and are asynchronous on `stream` (hipStream_t; NULL =
+ * default stream): they make no allocation, no host synchronisation and no copy.  gi_render_aov and
+ * gi_camera_rays do the same from / into host buffers (stage, launch, copy back) and are synchronous.
+ * Scene state: as the ray queries -- only the scene's immutable records are read, none of its Mode X
+ * scratch is touched, the calls are not ordered against the scene's renders, and a call between two
+ * progressive passes does not end the progressive frame.
+ * Not provided: jittered or per-sample feature buffers (one unjittered ray per pixel); Mode R's
+ * last-hit-wins choice (gi_trace_ray serves it); shard packing / gi_multi (a whole frame is one coherent
+ * ray per pixel on one device). */
+typedef struct gi_aov_frame { int32_t w, h, x0, y0, x1, y1; } gi_aov_frame;   /* window of a w x h frame */
+typedef struct gi_aov { double* t; double* normal; double* albedo; int32_t* prim; int32_t* entity; int32_t* uv; } gi_aov;
+int gi_render_aov_device(gi_scene* scene, const gi_camera* cam, const gi_aov_frame* frame, const gi_aov* d_out,
+                         void* stream);
+int gi_render_aov(gi_scene* scene, const gi_camera* cam, const gi_aov_frame* frame, const gi_aov* out);
+int gi_camera_rays_device(const gi_camera* cam, const gi_aov_frame* frame, double* d_rays, void* stream);
+int gi_camera_rays(const gi_camera* cam, const gi_aov_frame* frame, double* rays);
 
 /* Average duration in ms of the dominant kernel over the scene's renders issued with GI_FLAG_TIME
  * since the previous call (waits for the last one; *n = how many, may be NULL), then resets.
