@@ -190,41 +190,53 @@ __device__ __forceinline__ int wf_trace(float far_r, NodeP W, HotP H, V3 o, V3 d
 //  Phase A, uniform over the wave: every record of the leaf table (DevScene::xflat) is read at a
 //    wave-uniform address -- through the constant cache, so its eight words are scalar operands -- and
 //    its box tested for every lane with child_hit's arithmetic against [0, tmax]; leaves of the ray's
-//    own plane group are dropped as children_mask<AXIS, true> drops them.  Hit leaves set their bit in
-//    the lane's candidate mask.  Closest hit: the nearest candidate (entry distance tn1) and the second
-//    smallest entry distance tn2 are kept.  Any hit: the last candidate found.
-//  Phase B, per lane: the PAIR leaf block of wf_trace on one candidate per iteration.  Closest hit:
-//    the nearest candidate first; a lane whose best t lies in front of tn2 is finished (no other box
-//    reaches it); otherwise the remaining candidates in bit order, each re-tested against the current
-//    best t (a per-lane read of its record) before its exact tests.  Any hit: candidates from the
-//    highest bit down until one is hit.
+//    own plane group are dropped as children_mask<AXIS, true> drops them.  Every leaf shifts its hit
+//    bit into the lane's candidate mask.  Closest hit: the two smallest keys of the candidates are kept,
+//    a key being the entry distance with the leaf index in its low five bits -- so the nearest
+//    candidate travels with its distance, to within 31 ulp.  Nothing else is carried per leaf.
+//  Phase B, per lane: the PAIR leaf block of wf_trace on one candidate per iteration, its (offset,
+//    count) read per lane from the table.  Closest hit: the smallest key's leaf first; a lane whose best
+//    t lies in front of the second key's floor is finished (no other box reaches it); otherwise the
+//    remaining candidates in bit order, each re-tested against the current best t (a per-lane read of
+//    its record) before its exact tests.  Any hit: candidates from the lowest bit up (the highest leaf
+//    first) until one is hit.
+//  The keys round entry distances, which only orders the candidates; the one decision taken on a key,
+//    the early exit, compares a value that is not above any remaining candidate's true entry distance.
 // Exactness: the closest hit is the (t, primitive) minimum over all primitives whatever the order,
 // a leaf is left out only by the conservative box test or the own-plane rule the tree walk uses,
 // and the shadow answer is a boolean.
 // STATS: nnode counts the 256-byte units of the table a query reads, nsteps Phase B's iterations.
-#ifndef GI_XFLAT_CHUNK
-#define GI_XFLAT_CHUNK 0
-#endif
-#ifndef GI_XFLAT_UNROLL
-#define GI_XFLAT_UNROLL 4   // Phase A records in flight (their loads overlap the previous records' tests)
-#endif
-#ifndef GI_XFLAT_LDS
-#define GI_XFLAT_LDS 0   // (A/B builds) 1: the flat query reads a copy of its leaf table staged in LDS (wf_stage)
-#endif
+constexpr size_t kFlatPkBytes = GI_XFLAT_MAX * sizeof(uint32_t);   // the leaves' candidate words in LDS (wf_stage)
 typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
-// record k's eight words from the constant address space: a scalar load at a uniform address
-// (GI_XFLAT_LDS: from the table's copy staged in LDS, a broadcast read per record)
+// record k's eight words from the constant address space: a scalar load at a uniform address (a copy
+// of the table staged in LDS and read by broadcast measured 2.5% slower on the Cornell box, round 8)
 __device__ __forceinline__ u32x8 flat_rec_uniform(const XFlatLeaf* tab, int k) {
-#if GI_XFLAT_LDS
-    const int4* q = reinterpret_cast<const int4*>(tab + k);
-    const int4 a = q[0], b = q[1];
-    return u32x8{(uint32_t)a.x, (uint32_t)a.y, (uint32_t)a.z, (uint32_t)a.w, (uint32_t)b.x, (uint32_t)b.y, (uint32_t)b.z, (uint32_t)b.w};
-#else
     return *(const __attribute__((address_space(4))) u32x8*)(uintptr_t)(tab + k);
-#endif
 }
 // (offset, index, count) of a candidate in one word: offset < 2^16, count <= 255 (HostScene::x_flat_ok)
 __device__ __forceinline__ uint32_t flat_pack(uint32_t off, int k, uint32_t w7) { return off | ((uint32_t)k << 16) | ((w7 & 0xFFu) << 24); }
+// Phase A's per-leaf bookkeeping, one instruction each.  The compiler has no single-instruction form for
+// either from C++ (it selects a 0/1 select + shift-or, and an and + or), hence the two asm lines.
+//  flat_shift_in: m + m + (the lane's bit of the wave mask hm) -- an add with carry-in.
+//  flat_key: the entry distance's bits with the low five replaced by the leaf index k (uniform, < 32).
+__device__ __forceinline__ uint32_t flat_shift_in(uint32_t m, unsigned long long hm) {
+    uint32_t r;
+    asm("v_addc_co_u32 %0, vcc, %1, %1, %2" : "=v"(r) : "v"(m), "s"(hm) : "vcc");
+    return r;
+}
+__device__ __forceinline__ int flat_key(float tn, int k) {
+    int r;
+    asm("v_bfi_b32 %0, 31, %1, %2" : "=v"(r) : "s"(k), "v"(tn));
+    return r;
+}
+// the middle of three (selected as one v_med3_i32)
+__device__ __forceinline__ int flat_med3(int a, int b, int c) { return max(min(a, b), min(max(a, b), c)); }
+// a key without its index bits: not above the entry distance it was made from
+__device__ __forceinline__ float flat_key_floor(int e) { return __int_as_float(e & ~31); }
+// (offset, index, count) of leaf k, read per lane from the words wf_stage packed into LDS (the flat query
+// runs on scenes staged in LDS only): an LDS read where a read of the table record in global memory put
+// a cache round trip on every query's path (C3 3.31 -> 3.29 ms, round 8)
+__device__ __forceinline__ uint32_t flat_pk_of(const uint32_t* pkw, int k) { return pkw[k]; }
 // child_hit on a table record read per lane
 __device__ __forceinline__ bool flat_hit(const XFlatLeaf* r, F3 no, F3 ivf, int sm, float tmax, uint32_t& pk, int k) {
     const int4* q = reinterpret_cast<const int4*>(r);
@@ -242,7 +254,7 @@ __device__ __forceinline__ bool flat_hit(const XFlatLeaf* r, F3 no, F3 ivf, int 
     return tn <= tf;
 }
 template <bool ANY, bool TRI>
-__device__ __forceinline__ int wf_flat(float far_r, const XFlatLeaf* tab, int n, const XHot* H, V3 o, V3 d, double tmax, bool act,
+__device__ __forceinline__ int wf_flat(float far_r, const XFlatLeaf* tab, const uint32_t* pkw, int n, const XHot* H, V3 o, V3 d, double tmax, bool act,
                                        double& t_out, uint32_t& nnode, uint32_t& nprim, uint32_t& nsteps, int skip) {
     const F3 of = ray_org32(o, d, far_r);
     const F3 ivf = inv_dir(d);
@@ -253,9 +265,15 @@ __device__ __forceinline__ int wf_flat(float far_r, const XFlatLeaf* tab, int n,
     float tbf = up32(tmax);
     int best = -1;
     // ---- phase A (a lane without a ray: an empty interval, no candidates)
-    const float tfa = act ? tbf : -1.0f;
+    // (canonical here, once: the minimum it enters would otherwise quiet it again for every leaf)
+    const float tfa = __builtin_canonicalizef(act ? tbf : -1.0f);
+    // m: the hit bits shifted in, so leaf k ends at bit n - 1 - k.  Closest hit: e1 <= e2, the two
+    // smallest candidate keys -- the entry distance's bits (tn >= 0: ordered as integers; -0 sorts first,
+    // which is its place) with the low five overwritten by the leaf index, so min / med3 carry the
+    // candidate along.  A key lies within 31 ulp of its tn on either side; flat_key_floor(key) <= tn.
+    constexpr int kNone = 0x7F800000;   // +inf: no candidate
     uint32_t m = 0, pk = 0;
-    float tn1 = INFINITY, tn2 = INFINITY;
+    int e1 = kNone, e2 = kNone;
     auto step = [&](const u32x8 w, int k) {
         const float lx = __uint_as_float(w[0]), ly = __uint_as_float(w[1]), lz = __uint_as_float(w[2]);
         const float hx = __uint_as_float(w[3]), hy = __uint_as_float(w[4]), hz = __uint_as_float(w[5]);
@@ -266,21 +284,20 @@ __device__ __forceinline__ int wf_flat(float far_r, const XFlatLeaf* tab, int n,
         const float az = __builtin_fmaf(lz, ivf.z, no.z), bz = __builtin_fmaf(hz, ivf.z, no.z);
         const float tn = fmaxf(fmaxf(sx ? bx : ax, sy ? by : ay), fmaxf(sz ? bz : az, 0.0f));
         const float tf = fminf(fminf(sx ? ax : bx, sy ? ay : by), fminf(sz ? az : bz, tfa));
-        const bool hit = (tn <= tf) & ((int)((w[7] >> 16) & 0xFFu) != skip);
-        const uint32_t pkk = flat_pack(w[6], k, w[7]);
-        m |= hit ? 1u << k : 0u;
-        if (ANY) {
-            pk = hit ? pkk : pk;
-        } else {
-            const float th = hit ? tn : INFINITY;
-            pk = th < tn1 ? pkk : pk;
-            tn2 = __builtin_amdgcn_fmed3f(tn1, tn2, th);   // (tn1 <= tn2: the middle is the second smallest)
-            tn1 = fminf(tn1, th);
+        const bool in = tn <= tf, other = (int)((w[7] >> 16) & 0xFFu) != skip;
+        // (the two compares' wave masks, so that their conjunction is the add's carry-in as it stands)
+        m = flat_shift_in(m, __builtin_amdgcn_ballot_w64(in) & __builtin_amdgcn_ballot_w64(other));
+        if (!ANY) {
+            const int key = flat_key(tn, k);   // (outside the select: asm is not speculated)
+            const int eh = (in & other) ? key : kNone;
+            e2 = flat_med3(e1, e2, eh);   // (e1 <= e2: the middle is the second smallest)
+            e1 = min(e1, eh);
         }
     };
+    // four records at a time, written out: the wave masks of step() are convergent operations, which the
+    // compiler does not unroll around when the trip count is a run-time value
     int k0 = 0;
-#if GI_XFLAT_CHUNK
-    for (; k0 + 4 <= n; k0 += 4) {   // four records' loads in flight, then their tests
+    for (; k0 + 4 <= n; k0 += 4) {
         const u32x8 w0 = flat_rec_uniform(tab, k0), w1 = flat_rec_uniform(tab, k0 + 1);
         const u32x8 w2 = flat_rec_uniform(tab, k0 + 2), w3 = flat_rec_uniform(tab, k0 + 3);
         step(w0, k0);
@@ -289,14 +306,18 @@ __device__ __forceinline__ int wf_flat(float far_r, const XFlatLeaf* tab, int n,
         step(w3, k0 + 3);
     }
 #pragma unroll 1
-#else
-#pragma unroll GI_XFLAT_UNROLL
-#endif
     for (int k = k0; k < n; ++k) step(flat_rec_uniform(tab, k), k);
     if (act) nnode += (uint32_t)((n * (int)sizeof(XFlatLeaf) + 255) / 256);
     // ---- phase B
     bool go = m != 0;
-    if (go) m &= ~(1u << ((pk >> 16) & 0xFFu));
+    if (go) {   // the first candidate: any hit, the lowest bit (the highest leaf, the order of the table's
+                // unshifted mask: on the Cornell box it finds an occluder a quarter of an iteration sooner
+                // than the reverse); closest hit, the smallest key's leaf (a candidate that begins at
+                // infinity has no key: without a keyed one, the lowest bit)
+        const int bit = (ANY || e1 == kNone) ? __builtin_ctz(m) : n - 1 - (e1 & 31);
+        m &= ~(1u << bit);
+        pk = flat_pk_of(pkw, n - 1 - bit);
+    }
     while (go) {
         ++nsteps;
         const int cnt = (int)(pk >> 24);
@@ -325,17 +346,19 @@ __device__ __forceinline__ int wf_flat(float far_r, const XFlatLeaf* tab, int n,
         go = false;
         if (ANY) {
             if (best < 0 && m != 0) {
-                const int k = 31 - __builtin_clz(m);
-                m &= ~(1u << k);
-                const int4 b = reinterpret_cast<const int4*>(tab + k)[1];
-                pk = flat_pack((uint32_t)b.z, k, (uint32_t)b.w);
+                const int bit = __builtin_ctz(m);
+                m &= m - 1;
+                pk = flat_pk_of(pkw, n - 1 - bit);
                 go = true;
             }
         } else {
-            if (tn2 > tbf) m = 0;   // every other candidate's box begins behind the best t
+            // every other candidate's key is at least e2, so its box begins at flat_key_floor(e2) or
+            // later: behind the best t
+            if (flat_key_floor(e2) > tbf) m = 0;
             while (m != 0) {
-                const int k = __builtin_ctz(m);
-                m &= m - 1;
+                const int bit = 31 - __builtin_clz(m);   // (the lowest leaf first, as the unshifted mask went)
+                m &= ~(1u << bit);
+                const int k = n - 1 - bit;
                 if (flat_hit(tab + k, no, ivf, sm, tbf, pk, k)) {
                     go = true;
                     break;
@@ -360,8 +383,8 @@ struct WFArgs {
 
 // The scene views of a bounce / segment kernel.  LDS (sc.x_lds_bytes > 0): the workgroup stages the
 // traversal records (wide nodes, leaf records) and the shading records (primitives, entities) at the
-// start of its dynamic LDS, so neither the traversal nor the shading issues a global load (with
-// GI_XFLAT_LDS the flat leaf table too, after the entities); then the per-lane path slots.
+// start of its dynamic LDS, so neither the traversal nor the shading issues a global load; then the
+// per-lane path slots.
 // HBM-resident scenes: the per-lane level stack (16 x 256 ints), then the path slots.
 struct WFView {
     const XWNode* LW = nullptr;
@@ -369,10 +392,11 @@ struct WFView {
     const XPrim* XP = nullptr;
     const REnt* EN = nullptr;
     const XFlatLeaf* FT = nullptr;   // the flat leaf table phase A reads
+    const uint32_t* FP = nullptr;    // FLAT: per leaf its (offset, index, count) word, in LDS (flat_pk_of)
     int* nst = nullptr;
     double* pl = nullptr;   // this lane's L (fields 0-2) and T (3-5), pl[f * 256]
 };
-template <bool LDS>
+template <bool LDS, bool FLAT = false>
 __device__ __forceinline__ WFView wf_stage(const DevScene& sc, int4* lds) {
     WFView v;
     v.XP = sc.xprims;
@@ -383,24 +407,27 @@ __device__ __forceinline__ WFView wf_stage(const DevScene& sc, int4* lds) {
         const int nh = sc.n_xhot * (int)(sizeof(XHot) / sizeof(int4));
         const int np = sc.n_xprims * (int)(sizeof(XPrim) / sizeof(int4));
         const int ne = sc.n_ents * (int)(sizeof(REnt) / sizeof(int4));
-        const int nf = GI_XFLAT_LDS ? sc.n_xflat * (int)(sizeof(XFlatLeaf) / sizeof(int4)) : 0;
         const int4* gw = reinterpret_cast<const int4*>(sc.xwnodes);
         const int4* gh = reinterpret_cast<const int4*>(sc.xhot);
         const int4* gp = reinterpret_cast<const int4*>(sc.xprims);
         const int4* ge = reinterpret_cast<const int4*>(sc.ents);
-        const int4* gf = reinterpret_cast<const int4*>(sc.xflat);
         for (int i = threadIdx.x; i < nw; i += blockDim.x) lds[i] = gw[i];
         for (int i = threadIdx.x; i < nh; i += blockDim.x) lds[nw + i] = gh[i];
         for (int i = threadIdx.x; i < np; i += blockDim.x) lds[nw + nh + i] = gp[i];
         for (int i = threadIdx.x; i < ne; i += blockDim.x) lds[nw + nh + np + i] = ge[i];
-        for (int i = threadIdx.x; i < nf; i += blockDim.x) lds[nw + nh + np + ne + i] = gf[i];
+        // FLAT: the leaves' candidate words behind the entities (kFlatPkBytes, counted by wf_scene_lds_bytes)
+        constexpr int nk = FLAT ? (int)(kFlatPkBytes / sizeof(int4)) : 0;
+        if constexpr (FLAT) {
+            uint32_t* pkw = reinterpret_cast<uint32_t*>(lds + nw + nh + np + ne);
+            for (int i = threadIdx.x; i < sc.n_xflat; i += blockDim.x) pkw[i] = flat_pack((uint32_t)sc.xflat[i].off, i, (uint32_t)sc.xflat[i].cnt);
+            v.FP = pkw;
+        }
         __syncthreads();
         v.LW = reinterpret_cast<const XWNode*>(lds);
         v.LH = reinterpret_cast<const XHot*>(lds + nw);
         v.XP = reinterpret_cast<const XPrim*>(lds + nw + nh);
         v.EN = reinterpret_cast<const REnt*>(lds + nw + nh + np);
-        if (GI_XFLAT_LDS) v.FT = reinterpret_cast<const XFlatLeaf*>(lds + nw + nh + np + ne);
-        v.pl = reinterpret_cast<double*>(lds + nw + nh + np + ne + nf) + threadIdx.x;
+        v.pl = reinterpret_cast<double*>(lds + nw + nh + np + ne + nk) + threadIdx.x;
     } else {
         v.nst = reinterpret_cast<int*>(lds) + threadIdx.x;   // 16 levels x 256 lanes
         v.pl = reinterpret_cast<double*>(reinterpret_cast<int*>(lds) + 16 * 256) + threadIdx.x;
@@ -471,7 +498,7 @@ __device__ __forceinline__ void wf_wave_steps(uint32_t n, uint64_t& it, uint64_t
 template <bool ANY, bool LDS, bool SH, bool TRI, bool CN, bool FLAT>
 __device__ __forceinline__ int x_query(const DevScene& sc, const WFView& v, float far_r, const V3& o, const V3& d, double tmax,
                                        bool act, double& t_out, uint32_t& nnode, uint32_t& nprim, uint32_t& st_steps, int skip) {
-    if constexpr (FLAT) return wf_flat<ANY, TRI>(far_r, v.FT, sc.n_xflat, v.LH, o, d, tmax, act, t_out, nnode, nprim, st_steps, skip);
+    if constexpr (FLAT) return wf_flat<ANY, TRI>(far_r, v.FT, v.FP, sc.n_xflat, v.LH, o, d, tmax, act, t_out, nnode, nprim, st_steps, skip);
     else if constexpr (LDS) return wf_trace<ANY, true, false, SH, TRI, false>(far_r, v.LW, v.LH, o, d, tmax, act, v.nst, t_out, nnode, nprim, st_steps, skip);
     else if constexpr (CN) return wf_trace<ANY, false, false, SH, TRI, true>(far_r, sc.xcnodes, sc.xhot, o, d, tmax, act, v.nst, t_out, nnode, nprim, st_steps);
     else return wf_trace<ANY, false, false, SH, TRI, true>(far_r, sc.xwnodes, sc.xhot, o, d, tmax, act, v.nst, t_out, nnode, nprim, st_steps, skip);
@@ -612,7 +639,7 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
     }
     if (*(volatile unsigned*)a.take >= n_in) return;   // nothing left (before staging the scene)
     extern __shared__ int4 lds_dyn[];
-    const WFView v = wf_stage<LDS>(sc, lds_dyn);
+    const WFView v = wf_stage<LDS, FLAT>(sc, lds_dyn);
     const bool no_shadow = (xflags & XF_NO_SHADOW) != 0;
     const int lane = threadIdx.x & 63;
     uint32_t nnode = 0, nprim = 0, nrays = 0, nres = 0, npx = 0;
@@ -725,7 +752,7 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
     DevScene sc, CamDev cam, V3 light, TileMap m, int spp, int depth, uint64_t seed, double* rgb, uint8_t* rgb8,
     unsigned long long* stats, WFArgs a, int xflags) {
     extern __shared__ int4 lds_dyn[];
-    const WFView v = wf_stage<LDS>(sc, lds_dyn);
+    const WFView v = wf_stage<LDS, FLAT>(sc, lds_dyn);
     const bool no_shadow = (xflags & XF_NO_SHADOW) != 0;
     const int lane = threadIdx.x & 63;
     const unsigned long long total = (unsigned long long)*a.n_list * (unsigned long long)a.ns;
@@ -879,7 +906,7 @@ template <bool LDS, bool W4, bool SH, bool TRI, bool CN, bool FLAT>
 __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_WAVES) void k_x_query_kat(
     DevScene sc, V3 cam_pos, int n, const double* recs, int32_t* oi, double* od) {
     extern __shared__ int4 lds_dyn[];
-    const WFView v = wf_stage<LDS>(sc, lds_dyn);
+    const WFView v = wf_stage<LDS, FLAT>(sc, lds_dyn);
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     const bool act = i < (long long)n;
     const double skip_cos = x_skip_cos(sc, cam_pos);
@@ -933,7 +960,7 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
 //    shifted point o + t0 d (t0 > 0) while tmax, like the best t it initialises in wf_trace and
 //    wf_flat (tb, tbf, phase A's tfa), counts from o.  A box that begins at s from the shifted point
 //    begins at s + t0 from o, so the exact bound from the shifted point would be tmax - t0; testing
-//    s against tmax itself only keeps more boxes, and wf_flat's early exit (tn2 > tbf) drops its
+//    s against tmax itself only keeps more boxes, and wf_flat's early exit (e2's floor > tbf) drops its
 //    other candidates only when they begin beyond tmax + t0.  The fp64 primitive tests take o, d and
 //    tmax as given, and compare t < tmax strictly (a first hit at t == tmax finds best = -1, which
 //    no primitive index is below): the interval is open at both ends.
@@ -944,7 +971,7 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
 template <bool ANY, bool LDS, bool W4, bool SH, bool TRI, bool CN, bool FLAT>
 __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_WAVES) void k_cast(DevScene sc, CastIO io) {
     extern __shared__ int4 lds_dyn[];
-    const WFView v = wf_stage<LDS>(sc, lds_dyn);
+    const WFView v = wf_stage<LDS, FLAT>(sc, lds_dyn);
     const int lane = threadIdx.x & 63;
     const long long stride = 64ll * (long long)gridDim.x * (long long)(blockDim.x >> 6);
     for (long long base = 64ll * ((long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)); base < io.n; base += stride) {
@@ -1035,7 +1062,7 @@ __device__ __forceinline__ bool aov_pixel(int cols, int rows, long long b, int l
 template <bool LDS, bool W4, bool SH, bool TRI, bool CN, bool FLAT>
 __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_WAVES) void k_aov(DevScene sc, CamDev cam, AovIO io) {
     extern __shared__ int4 lds_dyn[];
-    const WFView v = wf_stage<LDS>(sc, lds_dyn);
+    const WFView v = wf_stage<LDS, FLAT>(sc, lds_dyn);
     const int lane = threadIdx.x & 63;
     const float far_r = ray_far_r(sc, cam.pos);   // (far cameras: gi_dev.h ray_org32)
     const long long n_batches = aov_batches(io.cols, io.rows);
@@ -1119,7 +1146,8 @@ size_t wf_slot_bytes() { return kWfSlotBytes; }
 // the scene's share of that LDS (LDS-resident scenes): the staged records (entity records included:
 // read from global memory by the shading instead, C3 4.65 -> 4.69 ms, and 5 waves per SIMD with them
 // there, 96 VGPRs and 120 B of scratch, 4.79 ms; profiles/r06_ab.txt)
-size_t wf_scene_lds_bytes(const DevScene& sc) { return (size_t)sc.x_lds_bytes + (GI_XFLAT_LDS ? (size_t)sc.n_xflat * sizeof(XFlatLeaf) : 0); }
+// (and, where the flat leaf query applies, its per-leaf candidate words)
+size_t wf_scene_lds_bytes(const DevScene& sc) { return (size_t)sc.x_lds_bytes + (sc.x_flat ? kFlatPkBytes : 0); }
 
 // The kernel variant for a scene: f(XTag) (var: XLaunchCfg::var; flat: the flat leaf query, LDS-resident
 // scenes whose table applies -- DevScene::x_flat -- unless GI_X_FLAT=0).  TRI of an LDS-resident scene is

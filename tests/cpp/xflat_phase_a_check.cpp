@@ -1,0 +1,422 @@
+// xflat_phase_a_check.cpp — CPU model of the flat leaf query's Phase A and Phase B as gi_wf.hip wf_flat
+// has them since round 8, over libgi's own host scene builder (gi_build.cpp + gi_bvh.cpp, compiled here
+// by g++), against brute force.
+//
+//  Phase A, per leaf k of the table (n leaves): child_hit's box arithmetic; the hit bit (box hit and not
+//    the ray's own plane group) is shifted into the mask, m = m + m + hit, so leaf k ends at bit n - 1 - k.
+//    Closest hit: key = the entry distance's bits with the low five replaced by k (+inf without a hit);
+//    e2 = med3(e1, e2, key), e1 = min(e1, key) as signed integers.  Nothing else is carried.
+//  Phase B: the first candidate is the lowest bit (any hit: the highest leaf) or leaf e1 & 31 (closest hit;
+//    the lowest bit when no candidate has a key); its (offset, count) come from its table record.  Closest hit: after a
+//    candidate's exact tests every other candidate is dropped when floor(e2) > up32(best t), floor
+//    clearing the five index bits; the rest go from the highest bit down (the lowest leaf first), each re-tested against the best t; the any
+//    hit goes on from the lowest bit up.
+//  Checked: (t, primitive) of the closest hit and the any-hit boolean equal brute force's for every ray.
+//  Scenes: soups of 1, 4, 5, 31 and 32 single-triangle leaves (the four-record loop's remainders and the
+//  mask's top bit) and the Cornell box (argv[2], a .scn file: 17 leaves, overlapping boxes).
+//  Rays: random and axis-parallel; origins inside a leaf's box (entry distance 0, for every box that
+//  holds the origin: keys that differ in the index only); rays aimed at the edge where two overlapping
+//  boxes' entry faces meet (entry distances a few ulp apart or equal -- counted, both classes must
+//  occur); rays leaving hit points with the own-plane skip at incidences on both sides of the bound;
+//  queries without a ray (a lane that carries none).
+//   xflat_phase_a_check <n_rays> cornell.scn
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <sstream>
+#include <string>
+#include <vector>
+
+#include "gi.h"
+#include "gi_scene.h"
+
+namespace gi {
+bool build_host_scene(const gi_scene_desc& desc, HostScene& hs, std::string& err);
+}
+using namespace gi;
+
+static uint64_t g_rng = 0x2019;
+static double urand() {
+    g_rng += 0x9E3779B97F4A7C15ULL;
+    uint64_t z = g_rng;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    z ^= z >> 31;
+    return (double)(z >> 11) * 0x1.0p-53;
+}
+
+static double prim_t(const XHot& p, V3 o, V3 d, double tmin) {   // the kernel's x_prim_t (triangles)
+    const V3 e1 = ld3(p.b), e2 = ld3(p.c);
+    const V3 pv = fcross(d, e2);
+    const double det = fdot(e1, pv);
+    if (det == 0.0) return INFINITY;
+    const V3 tv = o - ld3(p.a);
+    const double un = fdot(tv, pv);
+    if (det > 0.0 ? (un < 0.0 || un > det) : (un > 0.0 || un < det)) return INFINITY;
+    const V3 qv = fcross(tv, e1);
+    const double vn = fdot(d, qv);
+    const double uvn = un + vn;
+    if (det > 0.0 ? (vn < 0.0 || uvn > det) : (vn > 0.0 || uvn < det)) return INFINITY;
+    const double t = fdot(e2, qv) / det;
+    return (t > tmin) ? t : INFINITY;
+}
+static XHot hot_of(const XPrim& p, int i) {
+    XHot h;
+    for (int k = 0; k < 3; ++k) { h.a[k] = p.a[k]; h.b[k] = p.b[k]; h.c[k] = p.c[k]; }
+    h.prim = i;
+    h.kind = p.kind;
+    return h;
+}
+static float up32(double v) {
+    float f = (float)v;
+    if ((double)f < v) f = std::nextafter(f, INFINITY);
+    return f;
+}
+struct F3 { float x, y, z; };
+static float inv_clamp(float v) { return std::fmin(std::fmax(1.0f / v, -1e30f), 1e30f); }
+static int32_t bits_of(float f) { int32_t i; std::memcpy(&i, &f, 4); return i; }
+static float float_of(int32_t i) { float f; std::memcpy(&f, &i, 4); return f; }
+
+// child_hit's arithmetic on a table record; tn: the entry distance
+static bool flat_box(const XFlatLeaf& r, F3 no, F3 ivf, float tmax, float& tn) {
+    const bool sx = std::signbit(ivf.x), sy = std::signbit(ivf.y), sz = std::signbit(ivf.z);
+    const float ax = std::fmaf(r.lo[0], ivf.x, no.x), bx = std::fmaf(r.hi[0], ivf.x, no.x);
+    const float ay = std::fmaf(r.lo[1], ivf.y, no.y), by = std::fmaf(r.hi[1], ivf.y, no.y);
+    const float az = std::fmaf(r.lo[2], ivf.z, no.z), bz = std::fmaf(r.hi[2], ivf.z, no.z);
+    tn = std::fmax(std::fmax(sx ? bx : ax, sy ? by : ay), std::fmax(sz ? bz : az, 0.0f));
+    const float tf = std::fmin(std::fmin(sx ? ax : bx, sy ? ay : by), std::fmin(sz ? az : bz, tmax));
+    return tn <= tf;
+}
+static int32_t med3(int32_t a, int32_t b, int32_t c) { return std::max(std::min(a, b), std::min(std::max(a, b), c)); }
+static const int32_t kNone = 0x7F800000;
+static int32_t flat_key(float tn, int k) { return (int32_t)(((uint32_t)bits_of(tn) & ~31u) | (uint32_t)k); }
+static float key_floor(int32_t e) { return float_of(e & ~31); }
+
+static long g_iters = 0, g_cands = 0, g_queries = 0;
+static long g_tie0 = 0, g_tie32 = 0, g_inside = 0;   // rays by the two nearest candidates' entry distances
+// wf_flat; act: the lane carries a ray; skip: the ray's own plane group (254: none)
+static int flat_query(const HostScene& s, V3 o, V3 d, bool any, double tmax, bool act, double& t_out, int skip) {
+    const F3 of = {(float)o.x, (float)o.y, (float)o.z};
+    const F3 ivf = {inv_clamp((float)d.x), inv_clamp((float)d.y), inv_clamp((float)d.z)};
+    const F3 no = {-(of.x * ivf.x), -(of.y * ivf.y), -(of.z * ivf.z)};
+    double tb = tmax;
+    float tbf = up32(tmax);
+    int best = -1;
+    const int n = (int)s.xflat.size();
+    // ---- phase A
+    const float tfa = act ? tbf : -1.0f;
+    uint32_t m = 0;
+    int32_t e1 = kNone, e2 = kNone;
+    float d1 = INFINITY, d2 = INFINITY;   // (the class counters only: the true two smallest entry distances)
+    for (int k = 0; k < n; ++k) {
+        float tn;
+        const bool hit = flat_box(s.xflat[k], no, ivf, tfa, tn) & ((int)s.xflat[k].group != skip);
+        m = m + m + (hit ? 1u : 0u);
+        if (!any) {
+            const int32_t eh = hit ? flat_key(tn, k) : kNone;
+            e2 = med3(e1, e2, eh);
+            e1 = std::min(e1, eh);
+            if (hit) {
+                if (tn < d1) { d2 = d1; d1 = tn; }
+                else if (tn < d2) d2 = tn;
+            }
+        }
+    }
+    if (act) {
+        ++g_queries;
+        g_cands += __builtin_popcount(m);
+        if (!any && std::isfinite(d2)) {
+            const long ulps = (long)bits_of(d2) - (long)bits_of(d1);
+            if (ulps == 0) { ++g_tie0; if (d1 == 0.0f) ++g_inside; }
+            else if (ulps < 32) ++g_tie32;
+        }
+    }
+    // ---- phase B
+    bool go = m != 0;
+    int k = 0;
+    if (go) {
+        const int bit = (any || e1 == kNone) ? __builtin_ctz(m) : n - 1 - (e1 & 31);
+        if (bit < 0 || bit >= n || !(m & (1u << bit))) { std::printf("model: first candidate not in the mask\n"); std::exit(1); }
+        m &= ~(1u << bit);
+        k = n - 1 - bit;
+    }
+    while (go) {
+        ++g_iters;
+        const XFlatLeaf& lf = s.xflat[k];
+        for (int j = 0; j < lf.cnt; ++j) {
+            const XHot& h = s.xhot[lf.off + j];
+            const double t = prim_t(h, o, d, 1e-7);
+            if (any) {
+                if (t < tmax) { best = h.prim; break; }
+            } else if (t < tb || (t == tb && h.prim < best)) {
+                tb = t;
+                best = h.prim;
+                tbf = up32(tb);
+            }
+        }
+        go = false;
+        if (any) {
+            if (best < 0 && m != 0) {
+                const int bit = __builtin_ctz(m);
+                m &= m - 1;
+                k = n - 1 - bit;
+                go = true;
+            }
+        } else {
+            if (key_floor(e2) > tbf) m = 0;
+            while (m != 0) {
+                const int bit = 31 - __builtin_clz(m);
+                m &= ~(1u << bit);
+                k = n - 1 - bit;
+                float tn;
+                if (flat_box(s.xflat[k], no, ivf, tbf, tn)) { go = true; break; }
+            }
+        }
+    }
+    t_out = any ? INFINITY : tb;
+    return best;
+}
+
+static int brute(const HostScene& s, V3 o, V3 d, bool shadow, double tmax, double& tbest) {
+    tbest = INFINITY;
+    int best = -1;
+    for (size_t i = 0; i < s.xprims.size(); ++i) {
+        const double t = prim_t(hot_of(s.xprims[i], (int)i), o, d, 1e-7);
+        if (shadow) {
+            if (t < tmax) return (int)i;
+        } else if (t < tbest) {
+            tbest = t;
+            best = (int)i;
+        }
+    }
+    return best;
+}
+
+static gi_entity_desc tri(const double* v) {
+    gi_entity_desc e{};
+    e.kind = GI_IMP_TRIANGLE;
+    for (int k = 0; k < 9; ++k) e.args[k] = v[k];
+    return e;
+}
+// rows of eight small tilted triangles (tests/x_scenes.py soup): with GI_XLEAF_MAX=1, n leaves
+static void add_soup(std::vector<gi_entity_desc>& ents, int n) {
+    for (int i = 0; i < n; ++i) {
+        const double x = 3.0 + 0.1 * (i % 3), y = -3.5 + (i % 8), z = -2.0 + (i / 8);
+        const double v[9] = {x, y - 0.4, z - 0.4, x, y + 0.4, z - 0.4, x + 0.2, y, z + 0.4};
+        ents.push_back(tri(v));
+    }
+}
+static bool read_scn(const char* path, std::vector<gi_entity_desc>& ents) {
+    std::ifstream f(path);
+    std::string line;
+    while (std::getline(f, line)) {
+        std::istringstream is(line);
+        std::string kw;
+        is >> kw;
+        if (kw != "imptriangle") continue;
+        std::vector<double> v;
+        double x;
+        while (is >> x) v.push_back(x);
+        gi_entity_desc e{};
+        e.kind = GI_IMP_TRIANGLE;
+        for (size_t k = 0; k < v.size() && k < 11; ++k) e.args[k] = v[k];
+        ents.push_back(e);
+    }
+    return !ents.empty();
+}
+static bool build(std::vector<gi_entity_desc>& ents, HostScene& hs) {
+    gi_scene_desc sd{};
+    for (int k = 0; k < 3; ++k) { sd.octree_min[k] = -20; sd.octree_max[k] = 20; }
+    sd.n_entities = (int32_t)ents.size();
+    sd.entities = ents.data();
+    std::string err;
+    if (!build_host_scene(sd, hs, err)) { std::printf("build failed: %s\n", err.c_str()); return false; }
+    return true;
+}
+
+static bool same(bool shadow, int a, int b, double t1, double t2) {
+    return shadow ? ((a >= 0) == (b >= 0)) : (a == b && (t1 == t2 || (std::isinf(t1) && std::isinf(t2))));
+}
+static long check_one(const HostScene& hs, V3 o, V3 d, bool shadow, double tmax, int skip, const char* what, long& total) {
+    double t1, t2;
+    const int a = flat_query(hs, o, d, shadow, tmax, true, t1, skip);
+    const int b = brute(hs, o, d, shadow, tmax, t2);
+    ++total;
+    if (same(shadow, a, b, t1, t2)) return 0;
+    std::printf("%s mismatch: got %d want %d (t %.17g %.17g)\n", what, a, b, t1, t2);
+    return 1;
+}
+static V3 rand_dir() {
+    for (;;) {
+        const V3 v = v3(2 * urand() - 1, 2 * urand() - 1, 2 * urand() - 1);
+        const double q = sq3(v);
+        if (q > 1e-4 && q <= 1.0) return normalize(v);
+    }
+}
+// random and axis-parallel rays; every 16th query carries no ray
+static long check_rays(const HostScene& hs, int nrays, long& total) {
+    long bad = 0;
+    for (int r = 0; r < nrays; ++r) {
+        V3 o = (r % 2 == 0) ? v3(-10, 0, 0) : v3(urand() * 12 - 1, urand() * 12 - 6, urand() * 12 - 6);
+        V3 tgt = v3(urand() * 12 - 1, urand() * 12 - 6, urand() * 12 - 6);
+        if (r % 7 == 0) tgt.y = o.y;                    // one axis-parallel component
+        if (r % 21 == 0) tgt.z = o.z;                   // two
+        if (r % 63 == 0) { o = v3(-10, tgt.y, tgt.z); } // along +x
+        if (sq3(tgt - o) == 0.0) continue;
+        const V3 d = normalize(tgt - o);
+        const bool shadow = (r % 3) == 0;
+        const double tmax = shadow ? 3.0 + 10 * urand() : INFINITY;
+        if (r % 16 == 5) {   // a lane without a ray: no candidate, no hit
+            double t;
+            const long q0 = g_iters;
+            if (flat_query(hs, o, d, shadow, tmax, false, t, 254) != -1 || g_iters != q0) {
+                std::printf("a query without a ray found candidates\n");
+                ++bad;
+            }
+            continue;
+        }
+        bad += check_one(hs, o, d, shadow, tmax, 254, "ray", total);
+    }
+    return bad;
+}
+// origins inside a leaf's box (entry distance 0 for every box that holds the origin), random and
+// axis-parallel directions
+static long check_inside(const HostScene& hs, int nrays, long& total) {
+    long bad = 0;
+    const int n = (int)hs.xflat.size();
+    for (int r = 0; r < nrays && n > 0; ++r) {
+        const XFlatLeaf& f = hs.xflat[r % n];
+        const V3 o = v3(f.lo[0] + urand() * (f.hi[0] - f.lo[0]), f.lo[1] + urand() * (f.hi[1] - f.lo[1]),
+                        f.lo[2] + urand() * (f.hi[2] - f.lo[2]));
+        V3 d = rand_dir();
+        if (r % 5 == 0) d = v3(r % 2 ? 1 : -1, 0, 0);
+        if (r % 5 == 1) d = normalize(v3(0, d.y, d.z));
+        const bool shadow = (r % 3) == 0;
+        bad += check_one(hs, o, d, shadow, shadow ? 0.5 + 8 * urand() : INFINITY, 254, "inside", total);
+    }
+    return bad;
+}
+// rays through a point where the entry faces of two overlapping boxes meet: the two candidates' entry
+// distances agree to rounding (a few ulp, or exactly)
+static long check_near_ties(const HostScene& hs, int nrays, long& total) {
+    long bad = 0;
+    const int n = (int)hs.xflat.size();
+    std::vector<std::pair<int, int>> pairs;
+    for (int a = 0; a < n; ++a)
+        for (int b = a + 1; b < n; ++b) {
+            bool ov = true;
+            for (int k = 0; k < 3; ++k)
+                ov = ov && std::max(hs.xflat[a].lo[k], hs.xflat[b].lo[k]) < std::min(hs.xflat[a].hi[k], hs.xflat[b].hi[k]);
+            if (ov) pairs.push_back({a, b});
+        }
+    for (int r = 0; r < nrays && !pairs.empty(); ++r) {
+        const XFlatLeaf& A = hs.xflat[pairs[r % pairs.size()].first];
+        const XFlatLeaf& B = hs.xflat[pairs[r % pairs.size()].second];
+        double lo[3], hi[3], p[3];
+        for (int k = 0; k < 3; ++k) {
+            lo[k] = std::max(A.lo[k], B.lo[k]);
+            hi[k] = std::min(A.hi[k], B.hi[k]);
+            p[k] = lo[k] + urand() * (hi[k] - lo[k]);
+        }
+        // A is entered through its face on axis a, B through its face on axis b, at the same point
+        const int a = (r / 3) % 3, b = (a + 1 + (r % 2)) % 3;
+        const bool a_lo = (r / 7) % 2 == 0, b_lo = (r / 11) % 2 == 0;
+        p[a] = a_lo ? A.lo[a] : A.hi[a];
+        p[b] = b_lo ? B.lo[b] : B.hi[b];
+        if (p[a] < lo[a] || p[a] > hi[a] || p[b] < lo[b] || p[b] > hi[b]) continue;   // that face lies outside the other box
+        double dv[3] = {2 * urand() - 1, 2 * urand() - 1, 2 * urand() - 1};
+        dv[a] = (a_lo ? 1 : -1) * (0.2 + urand());
+        dv[b] = (b_lo ? 1 : -1) * (0.2 + urand());
+        if (r % 4 == 0) dv[3 - a - b] = 0.0;   // in the plane of the two axes
+        const V3 d = normalize(v3(dv[0], dv[1], dv[2]));
+        const double s = 0.5 + 6 * urand();
+        const V3 o = v3(p[0], p[1], p[2]) - d * s;
+        bad += check_one(hs, o, d, false, INFINITY, 254, "near tie", total);
+        if (r % 3 == 0) bad += check_one(hs, o, d, true, s + 4 * urand(), 254, "near tie (any hit)", total);
+    }
+    return bad;
+}
+// rays leaving computed hit points, the origin's plane group skipped when the incidence clears the bound
+static long check_plane_skip(const HostScene& hs, int nrays, long& skipped, long& unskipped, long& total) {
+    long bad = 0;
+    const int np = (int)hs.xprims.size();
+    for (int r = 0; r < nrays && np > 0; ++r) {
+        const int i = (int)(urand() * np) % np;
+        const XPrim& x = hs.xprims[i];
+        if (x.kind != 0 || x.pad[0] == 255) continue;
+        const V3 o = (r % 4 == 0) ? v3(-10, 0, 0) : v3(urand() * 12 - 1, urand() * 12 - 6, urand() * 12 - 6);
+        double a = urand(), b = urand();
+        if (a + b > 1) { a = 1 - a; b = 1 - b; }
+        const V3 tgt = ld3(x.a) + ld3(x.b) * a + ld3(x.c) * b;
+        const V3 d = normalize(tgt - o);
+        const double t = prim_t(hot_of(x, i), o, d, 1e-7);
+        if (!std::isfinite(t)) continue;
+        const V3 P = o + t * d;   // as x_segment computes the hit point
+        const V3 nn = ld3(x.n);
+        const double cmin = hs.x_skip_a * std::max(std::fabs(o.x), std::max(std::fabs(o.y), std::fabs(o.z))) + hs.x_skip_b;
+        V3 d2;
+        double tmax = INFINITY;
+        const int kind = r % 5;
+        if (kind == 0) {   // shadow ray toward a random point
+            const V3 L = v3(urand() * 12 - 1, urand() * 12 - 6, urand() * 12 - 6);
+            tmax = std::sqrt(sq3(L - P));
+            d2 = normalize(L - P);
+        } else {           // incidence c: a tangent direction tilted to |d . n| = c, either side of the plane
+            const double c = kind == 1 ? urand() : kind == 2 ? cmin * (1.0 + 3.0 * urand()) : kind == 3 ? cmin * (1.0 + 1e-3 * urand()) : cmin * 0.5;
+            V3 tg = cross(nn, v3(urand() - 0.5, urand() - 0.5, urand() - 0.5));
+            if (sq3(tg) == 0.0) continue;
+            tg = normalize(tg);
+            const double sg = urand() < 0.5 ? -1.0 : 1.0;
+            d2 = normalize(tg * std::sqrt(std::max(0.0, 1.0 - c * c)) + nn * (sg * c));
+        }
+        const int skip = std::fabs(dot(d2, nn)) >= cmin ? x.pad[0] : 254;
+        (skip != 254 ? skipped : unskipped) += 1;
+        bad += check_one(hs, P, d2, kind == 0, tmax, skip, "plane skip", total);
+    }
+    return bad;
+}
+
+int main(int argc, char** argv) {
+    if (argc < 3) { std::printf("usage: xflat_phase_a_check <n_rays> cornell.scn\n"); return 2; }
+    const int nrays = std::atoi(argv[1]);
+    long mism = 0, total = 0;
+    const int soups[5] = {1, 4, 5, 31, 32};
+    for (int scene = 0; scene < 6; ++scene) {
+        std::vector<gi_entity_desc> ents;
+        HostScene hs;
+        int want = 17;
+        if (scene < 5) {
+            setenv("GI_XLEAF_MAX", "1", 1);
+            add_soup(ents, want = soups[scene]);
+        } else {
+            unsetenv("GI_XLEAF_MAX");
+            if (!read_scn(argv[2], ents)) return 2;
+        }
+        if (!build(ents, hs)) return 2;
+        const int leaves = (int)hs.xflat.size();
+        if (leaves != want || !hs.x_flat_ok) { std::printf("scene %d: %d leaves (want %d), eligible %d\n", scene, leaves, want, (int)hs.x_flat_ok); return 1; }
+        const long q0 = g_queries, i0 = g_iters, c0 = g_cands, z0 = g_tie0, z1 = g_tie32, z2 = g_inside;
+        long t0 = 0, skipped = 0, unskipped = 0;
+        long bad = check_rays(hs, nrays, t0);
+        bad += check_inside(hs, nrays / 2, t0);
+        bad += check_near_ties(hs, nrays, t0);
+        bad += check_plane_skip(hs, 4 * nrays, skipped, unskipped, t0);
+        mism += bad;
+        total += t0;
+        std::printf("scene %d: %zu prims, %d leaves; %ld rays (%ld skipping their plane, %ld not); two nearest entry distances equal %ld"
+                    " (%ld at 0), within 32 ulp %ld; per query %.2f candidates, %.2f exact-test iterations; mismatches %ld\n",
+                    scene, hs.xprims.size(), leaves, t0, skipped, unskipped, g_tie0 - z0, g_inside - z2, g_tie32 - z1,
+                    (double)(g_cands - c0) / (double)std::max(1l, g_queries - q0),
+                    (double)(g_iters - i0) / (double)std::max(1l, g_queries - q0), bad);
+        if (scene == 5 && (g_tie0 - z0 - (g_inside - z2) == 0 || g_tie32 - z1 == 0 || g_inside - z2 == 0 || skipped == 0 || unskipped == 0)) {
+            std::printf("scene 5: a ray class is empty\n");
+            return 1;
+        }
+    }
+    std::printf("rays %ld mismatches %ld\n", total, mism);
+    return mism == 0 ? 0 : 1;
+}
