@@ -66,7 +66,7 @@ STAT_X_IT_RS, STAT_X_LN_RS, STAT_X_IT_ST, STAT_X_LN_ST = 20, 21, 22, 23
 STAT_R_PAIRS, STAT_R_OVF_TILES = 24, 25
 STATS_N = 26
 TILE = 8
-ABI_VERSION = 13
+ABI_VERSION = 14
 RAY_DOUBLES = 8   # a ray record of the batched queries: o[3], d[3], tmax, reserved (gi.h GI_RAY_DOUBLES)
 # the feature buffers of DeviceScene.render_aov (gi.h gi_aov, in its field order): name -> (dtype, trailing shape)
 AOV_OUTPUTS = ("t", "normal", "albedo", "prim", "entity", "uv")
@@ -129,7 +129,7 @@ TILE_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ct
 
 EXPORTS = ["gi_abi_version", "gi_last_error", "gi_camera_init", "gi_scene_create", "gi_scene_destroy",
            "gi_scene_get_info", "gi_render", "gi_render_device", "gi_shard_tiles", "gi_unshard_device",
-           "gi_trace_ray", "gi_kat_expbox", "gi_kat_x_query", "gi_kat_x_variant", "gi_scene_kernel_ms", "gi_scene_x_form", "gi_scene_r_kernel", "gi_octree_create", "gi_octree_destroy",
+           "gi_trace_ray", "gi_kat_expbox", "gi_kat_x_query", "gi_kat_x_variant", "gi_scene_kernel_ms", "gi_scene_x_form", "gi_scene_seg_ring", "gi_scene_r_kernel", "gi_octree_create", "gi_octree_destroy",
            "gi_octree_intersect", "gi_multi_create", "gi_multi_destroy", "gi_multi_info", "gi_multi_render", "gi_device_count",
            "gi_device_list", "gi_build_id", "gi_obj_parse", "gi_intersect", "gi_occluded", "gi_intersect_device",
            "gi_occluded_device", "gi_render_aov", "gi_render_aov_device", "gi_camera_rays", "gi_camera_rays_device"]
@@ -182,6 +182,7 @@ def lib():
         L.gi_camera_rays_device.argtypes = [ctypes.POINTER(CameraDesc), ctypes.POINTER(AovFrame), vp, vp]
         L.gi_scene_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)]
         L.gi_scene_x_form.argtypes = [vp, ctypes.POINTER(Opts), ctypes.POINTER(ctypes.c_int32)]
+        L.gi_scene_seg_ring.argtypes = [vp, ctypes.POINTER(Opts), ctypes.POINTER(ctypes.c_int32)]
         L.gi_scene_r_kernel.argtypes = [vp, ctypes.POINTER(Opts), ctypes.POINTER(ctypes.c_int32)]
         L.gi_octree_create.argtypes = [ctypes.POINTER(SceneDesc), ctypes.POINTER(vp)]
         L.gi_octree_destroy.argtypes = [vp]
@@ -559,6 +560,14 @@ class DeviceScene:
         f = ctypes.c_int32()
         _check(lib().gi_scene_x_form(self._h, ctypes.byref(o), ctypes.byref(f)), "gi_scene_x_form")
         return X_FORMS[f.value]
+
+    def seg_ring(self, mode=MODE_X, spp=1, depth=1, flags=0) -> bool:
+        """Whether a render with these options would run k_seg with its per-wave ring of prepared
+        primary rays (chosen per scene by LDS room; GI_SEG_RING=0 forces it off) -- gi_scene_seg_ring."""
+        o = self.opts(mode, spp, depth, 0, flags=flags)
+        f = ctypes.c_int32()
+        _check(lib().gi_scene_seg_ring(self._h, ctypes.byref(o), ctypes.byref(f)), "gi_scene_seg_ring")
+        return bool(f.value)
 
     def r_kernel(self, flags=0) -> str:
         """The Mode R kernel a render would run: "k_mode_r" (one lane per pixel), "k_rf_walk" (the flat

@@ -520,8 +520,10 @@ int scene_create_on(const gi_scene_desc* desc, int device, gi_scene** out) {
         d.x_flat = (d.x_lds_bytes > 0 && h.x_flat_ok) ? 1 : 0;
         // light shading (no acos texture mapping, no sphere primitives): gi_wf.hip's kernels (k_seg, k_cast)
         // run 4 waves per SIMD, provided four workgroups fit a CU's 160 KB.  The bound allows each, beside
-        // the scene, 256 lanes x 80 B and 4 x 68 x 4 B -- more than their path slots (256 x 72 B) need: it
-        // is the footprint of the LDS build k_mode_x once had, kept so that no scene changes its variant
+        // the scene, 256 lanes x 80 B and 4 x 68 x 4 B -- more than their path slots (256 x 64 B) need: it
+        // is the footprint of the LDS build k_mode_x once had, kept so that no scene changes its variant.
+        // (k_seg's ring of prepared primary rays, 10 KB more, is decided by the occupancy query of
+        // x_launch_config and changes no variant)
         const size_t per_wg = bytes + 256 * 10 * sizeof(double) + 4 * 68 * sizeof(unsigned);
         d.x_waves4 = (d.x_lds_bytes > 0 && 4 * per_wg <= 160 * 1024) ? 1 : 0;
         d.x_tri_only = 1;
@@ -774,6 +776,15 @@ int gi_scene_x_form(gi_scene* s, const gi_opts* o, int32_t* form) {
         if (!s || !o || !form) return fail(GI_ERR_ARG, "null argument");
         std::lock_guard<std::mutex> lk(s->mu);
         *form = x_form_choice(s->dev, s->xcfg, *o);
+        return GI_OK;
+    });
+}
+
+int gi_scene_seg_ring(gi_scene* s, const gi_opts* o, int32_t* on) {
+    return guard([&]() -> int {
+        if (!s || !o || !on) return fail(GI_ERR_ARG, "null argument");
+        std::lock_guard<std::mutex> lk(s->mu);
+        *on = (x_form_choice(s->dev, s->xcfg, *o) == 2 && s->xcfg.seg_ring) ? 1 : 0;
         return GI_OK;
     });
 }

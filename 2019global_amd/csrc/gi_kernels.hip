@@ -2146,10 +2146,11 @@ long long shard_tiles(int w, int h, int shard_count) { return make_map(w, h, sha
 // among kernels whose frames are identical bit for bit (tests/test_gpu_parity.py compares them):
 // GI_X_WF (0/1/2: force a Mode X form for a whole suite run), GI_X_HELP=0 (no shadow-ray handoff),
 // GI_X_FLAT=0 (k_seg / k_wf_bounce walk the tree even where the scene's flat leaf table applies),
+// GI_SEG_RING=0 (k_seg's lanes make their own units even where the per-wave ring fits),
 // GI_R_FLAT (0/1/2: force a Mode R kernel), GI_RF_PER_SLOT (the flat Mode R pool size: 0 forces the
 // per-tile overflow path), GI_RF_GROUP (1/4: force k_rf_reach's lanes per hit).
 struct XEnv {
-    int run_log2 = 0, help = 1, wf = -1, flat = 1;
+    int run_log2 = 0, help = 1, wf = -1, flat = 1, seg_ring = 1;
     int r_flat = -1;                  // Mode R kernels (GI_R_FLAT): 1 the flat phases for every scene, 0 k_mode_r
                                       // for every scene, 2 k_mode_r_batch for the whole frame (tests); -1 by size
     int rf_per_slot = 16;             // flat Mode R: pool pairs per pixel slot of the frame (GI_RF_PER_SLOT)
@@ -2161,6 +2162,7 @@ const XEnv& x_env() {
     std::call_once(once, [] {
         if (const char* v = std::getenv("GI_X_HELP")) env.help = std::atoi(v) != 0;
         if (const char* v = std::getenv("GI_X_FLAT")) env.flat = std::atoi(v) != 0;
+        if (const char* v = std::getenv("GI_SEG_RING")) env.seg_ring = std::atoi(v) != 0;
         if (const char* v = std::getenv("GI_R_FLAT")) env.r_flat = std::atoi(v);
         if (const char* v = std::getenv("GI_RF_PER_SLOT")) env.rf_per_slot = std::max(0, std::min(1024, std::atoi(v)));
         if (const char* v = std::getenv("GI_X_WF")) env.wf = std::atoi(v);
@@ -2181,7 +2183,8 @@ hipError_t launch_wf(const DevScene& sc, XVariant var, size_t lds_bytes, int res
                      hipEvent_t ev_begin, hipEvent_t ev_end);
 hipError_t wf_occupancy(const DevScene& sc, XVariant var, bool flat, size_t lds_bytes, int form, int* per_cu);
 size_t wf_slot_bytes();
-size_t wf_scene_lds_bytes(const DevScene& sc);
+size_t wf_scene_lds_bytes(const DevScene& sc, bool flat);
+size_t wf_seg_ring_bytes();
 
 #ifndef GI_WF_MAX_DEPTH
 #define GI_WF_MAX_DEPTH 64   // the wavefront form launches once per bounce: deeper paths run k_mode_x
@@ -2246,14 +2249,23 @@ hipError_t x_launch_config(const DevScene& sc, int device, XLaunchCfg& cfg) {
     });
     if (e != hipSuccess) return e;
     cfg.resident = std::max(1, cus) * std::max(1, per_cu);
-    cfg.wf_lds_bytes = (lds ? wf_scene_lds_bytes(sc) : 16 * 256 * sizeof(int)) + wf_slot_bytes();
     const bool flat = sc.x_flat && x_env().flat;   // (the launches' choice: launch_render's XF_NO_FLAT)
+    cfg.wf_lds_bytes = (lds ? wf_scene_lds_bytes(sc, flat) : 16 * 256 * sizeof(int)) + wf_slot_bytes();
+    cfg.wf_tree_lds_bytes = (lds ? wf_scene_lds_bytes(sc, false) : 16 * 256 * sizeof(int)) + wf_slot_bytes();
     e = wf_occupancy(sc, cfg.var, flat, cfg.wf_lds_bytes, 1, &per_cu);
     if (e != hipSuccess) return e;
     cfg.wf_resident = std::max(1, cus) * std::max(1, per_cu);
     e = wf_occupancy(sc, cfg.var, flat, cfg.wf_lds_bytes, 2, &per_cu);
     if (e != hipSuccess) return e;
     cfg.seg_resident = std::max(1, cus) * std::max(1, per_cu);
+    // k_seg's per-wave ring of prepared primary rays (gi_wf.hip): only where its LDS leaves the kernel's
+    // resident workgroups per CU as they are -- fewer waves cost more than the ring saves.  GI_SEG_RING=0
+    // (tests): never
+    int per_cu_ring = 0;
+    e = wf_occupancy(sc, cfg.var, flat, cfg.wf_lds_bytes + wf_seg_ring_bytes(), 6, &per_cu_ring);
+    if (e != hipSuccess) return e;
+    cfg.seg_ring = x_env().seg_ring && per_cu_ring >= per_cu && per_cu >= 1;
+    cfg.seg_lds_bytes = cfg.wf_lds_bytes + (cfg.seg_ring ? wf_seg_ring_bytes() : 0);
     e = wf_occupancy(sc, cfg.var, flat, cfg.wf_lds_bytes, 3, &per_cu);   // the ray queries (k_cast)
     if (e != hipSuccess) return e;
     cfg.cast_resident = std::max(1, cus) * std::max(1, per_cu);
@@ -2365,10 +2377,11 @@ hipError_t launch_render(const DevScene& sc, const XLaunchCfg& xc, const CamDev&
         const int h8 = sc.x_handle8;
         // schedule flags (XFlag, gi_scene.h): the scene's, the launch's and the maximum run length (log2)
         const int xf = sc.x_flags | (env.run_log2 << XF_RUN_SHIFT) | ((o.flags & GI_FLAG_X_NO_SHADOW) ? XF_NO_SHADOW : 0) |
-                       (env.help ? XF_HANDOFF : 0) | (help ? XF_SPREAD : 0) | XF_PIXEL_MAJOR | (env.flat ? 0 : XF_NO_FLAT);
+                       (env.help ? XF_HANDOFF : 0) | (help ? XF_SPREAD : 0) | XF_PIXEL_MAJOR | (env.flat ? 0 : XF_NO_FLAT) |
+                       (xc.seg_ring ? XF_SEG_RING : 0);
         if (form) {   // gi_wf.hip's forms, timed as one pass
             if (!xs.wcnt || (form == 1 && (!xs.wq[0] || !xs.wq[1] || xs.wcap <= 0))) return hipErrorInvalidValue;
-            e = launch_wf(sc, xc.var, xc.wf_lds_bytes, form == 2 ? xc.seg_resident : xc.wf_resident, form, cam, light, w, h, y0,
+            e = launch_wf(sc, xc.var, form == 2 ? xc.seg_lds_bytes : xc.wf_lds_bytes, form == 2 ? xc.seg_resident : xc.wf_resident, form, cam, light, w, h, y0,
                           o, rgb, rgb8, xs, sc.work + 1, stats ? st : nullptr, xf, stream, ev_begin, ev_end);
             if (e != hipSuccess) return e;
             if (o.spp > 1) hipLaunchKernelGGL(k_x_reduce, sgrid, dim3(256), 0, stream, m, wk, o.spp, rgb, rgb8);
@@ -2415,8 +2428,9 @@ struct XQueryCfg {
 };
 XQueryCfg x_query_cfg(const XLaunchCfg& xc, int flags) {
     const bool hbm = (flags & 2) != 0 && xc.var.lds;
-    return XQueryCfg{hbm ? XVariant{} : xc.var, hbm ? 16 * 256 * sizeof(int) + wf_slot_bytes() : xc.wf_lds_bytes,
-                     x_env().flat && (flags & 1) == 0};
+    const bool flat = x_env().flat && (flags & 1) == 0;
+    return XQueryCfg{hbm ? XVariant{} : xc.var,
+                     hbm ? 16 * 256 * sizeof(int) + wf_slot_bytes() : flat ? xc.wf_lds_bytes : xc.wf_tree_lds_bytes, flat};
 }
 }  // namespace
 hipError_t launch_x_query(const DevScene& sc, const XLaunchCfg& xc, V3 cam_pos, int flags, int n, const double* recs,

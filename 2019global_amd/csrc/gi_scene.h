@@ -308,6 +308,7 @@ enum XFlag : int {
     XF_SPREAD = 1 << 4,          // spread work groups (launches that run the handoff build)
     XF_PIXEL_MAJOR = 1 << 5,     // pixel-major work blocks
     XF_NO_FLAT = 1 << 6,         // GI_X_FLAT=0: gi_wf.hip's forms walk the tree although the flat leaf table applies
+    XF_SEG_RING = 1 << 7,        // k_seg refills from its per-wave ring of prepared primary rays (XLaunchCfg::seg_ring)
     XF_RUN_SHIFT = 8, XF_RUN_MASK = 7,   // bits 8-10: log2 of the maximum run length (GI_X_MAX_RUN)
 };
 
@@ -340,9 +341,12 @@ struct XLaunchCfg {
     XVariant var;            // gi_wf.hip's kernels: their variant
     size_t lds_bytes = 0;    // k_mode_x: dynamic LDS per workgroup (level stack and handoff slots, any scene)
     int resident = 1;        //   and its resident 256-thread workgroups on the device (occupancy x CUs)
-    size_t wf_lds_bytes = 0; // wavefront Mode X (k_wf_bounce, k_seg): dynamic LDS per workgroup
+    size_t wf_lds_bytes = 0; // gi_wf.hip's kernels (k_wf_bounce, k_cast, k_aov, the query KAT): dynamic LDS per workgroup
+    size_t wf_tree_lds_bytes = 0;   //   the same for the tree walk where the flat query is the default (the KAT's flag)
     int wf_resident = 1;     //   and the resident workgroups of k_wf_bounce
     int seg_resident = 1;    //   and of k_seg
+    bool seg_ring = false;   // k_seg refills from its per-wave ring: its LDS does not lower k_seg's resident workgroups
+    size_t seg_lds_bytes = 0;//   k_seg's dynamic LDS: wf_lds_bytes, and the ring's bytes with seg_ring
     int cast_resident = 1;   // the ray queries (k_cast, gi_wf.hip): closest hit
     int occl_resident = 1;   //   and any hit
     int aov_resident = 1;    // the feature buffers (k_aov, gi_wf.hip)

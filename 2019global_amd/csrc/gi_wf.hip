@@ -26,6 +26,7 @@
 #include "gi.h"
 #include "gi_dev.h"
 #include "gi_scene.h"
+#include "gi_seg_ring.h"
 
 namespace gi {
 namespace {
@@ -43,11 +44,19 @@ constexpr long long kWfTile = 8;   // pixel tiles are 8 x 8 (GI_TILE)
 #endif
 // a path's L and T wait out the two traversals in a per-lane LDS slot (column layout, 6 x 256 fp64 per
 // workgroup) instead of VGPRs: the 4-wave kernel stays within 128 VGPRs.  k_seg also keeps the path's
-// RNG key, its output index and sample, and its bounce there (fields 6, 7, 8), read where they are
-// used: carried in VGPRs across the traversals they were spilled to scratch (136 -> 56 B per lane).
+// RNG key and its output index and sample there (fields 6, 7), read where they are used: carried in
+// VGPRs across the traversals they were spilled to scratch (136 -> 56 B per lane).  The path's bounce
+// index rides in the high bits of k_seg's own-plane register (kSegPlaneBits).
 // LDS-resident scenes test leaf records two at a time (PAIR: two interleaved fp64 chains) and their
 // node slab tests issue the 12 loads at once (round 5: C3 4.90 -> 4.81 ms against axis by axis)
-constexpr size_t kWfSlotBytes = 9 * 256 * sizeof(double);
+constexpr size_t kWfSlotBytes = 8 * 256 * sizeof(double);
+// k_seg's per-wave ring of prepared primary rays, behind the path slots of launches that
+// carry it: five planes (d.x, d.y, d.z, key, idx | smp << 32) of 64 x 8 B per wave
+constexpr int kSegRingPlanes = 5;
+constexpr size_t kSegRingBytes = 4 * kSegRingPlanes * kSegBatch * sizeof(uint64_t);
+// k_seg's plane register: the own-plane skip of the lane's next ray in the low bits, the path's bounce
+// index (< 2^16, gi_capi.cpp) above them
+constexpr int kSegPlaneBits = 8, kSegPlaneMask = (1 << kSegPlaneBits) - 1;
 
 // a path's identity where the shading needs it: RNG key, sample, bounce
 struct PathId {
@@ -403,7 +412,8 @@ __device__ __forceinline__ WFView wf_stage(const DevScene& sc, int4* lds) {
     v.EN = sc.ents;
     v.FT = sc.xflat;
     if constexpr (LDS) {
-        const int nw = sc.n_xwnodes * (int)(sizeof(XWNode) / sizeof(int4));
+        // (FLAT: no kernel's flat query reads the wide nodes -- not staged, not counted by wf_scene_lds_bytes)
+        const int nw = FLAT ? 0 : sc.n_xwnodes * (int)(sizeof(XWNode) / sizeof(int4));
         const int nh = sc.n_xhot * (int)(sizeof(XHot) / sizeof(int4));
         const int np = sc.n_xprims * (int)(sizeof(XPrim) / sizeof(int4));
         const int ne = sc.n_ents * (int)(sizeof(REnt) / sizeof(int4));
@@ -423,7 +433,7 @@ __device__ __forceinline__ WFView wf_stage(const DevScene& sc, int4* lds) {
             v.FP = pkw;
         }
         __syncthreads();
-        v.LW = reinterpret_cast<const XWNode*>(lds);
+        if constexpr (!FLAT) v.LW = reinterpret_cast<const XWNode*>(lds);
         v.LH = reinterpret_cast<const XHot*>(lds + nw);
         v.XP = reinterpret_cast<const XPrim*>(lds + nw + nh);
         v.EN = reinterpret_cast<const REnt*>(lds + nw + nh + np);
@@ -537,8 +547,11 @@ __device__ __forceinline__ bool x_segment(const DevScene& sc, const WFView& v, c
     bool occl = false;
     // ---- closest hit
     double tbest = INFINITY;
-    // the own-plane skip of this ray (k_seg carries it from the previous segment; 254: none)
-    const int skip_c = splane ? *splane : 254;
+    // the own-plane skip of this ray (k_seg carries it from the previous segment; 254: none).  Only the
+    // low kSegPlaneBits of *splane are the plane: k_seg keeps its bounce index above them.  (Unpacking
+    // the plane in k_seg around this call instead was compiled: k_seg<false,true,true,false,true,false,
+    // false,false> then takes 84 B of scratch against 68 B, above the 76 B it had before the ring)
+    const int skip_c = splane ? (*splane & kSegPlaneMask) : 254;
     const int best = x_query<false, LDS, SH, TRI, CN, FLAT>(sc, v, far_r, o, d, INFINITY, act, tbest, nnode, nprim, st_steps, skip_c);
     if (act) ++nrays;
     if (STATS) {
@@ -616,7 +629,7 @@ __device__ __forceinline__ bool x_segment(const DevScene& sc, const WFView& v, c
         if (cont) {
             v.pl[0] = L.x; v.pl[256] = L.y; v.pl[512] = L.z;
             v.pl[768] = T.x; v.pl[1024] = T.y; v.pl[1280] = T.z;
-            if (splane) *splane = x_own_plane(h.pg, h.pn, d, skip_cos);
+            if (splane) *splane = (*splane & ~kSegPlaneMask) | x_own_plane(h.pg, h.pn, d, skip_cos);
         }
     }
     if (STATS) ws.cyc_sh += clock64() - c0;
@@ -747,7 +760,58 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
 #ifndef GI_SEG_TAKE_TRI
 #define GI_SEG_TAKE_TRI 1   // the same for LDS-resident triangle-only scenes (the Cornell box)
 #endif
-template <bool STATS, bool LDS, bool W4, bool SH, bool TRI, bool CN, bool FLAT>
+// Unit u of a k_seg launch, made: its work-list entry and sample, its primary ray (wf_primary), the
+// root-box pretest (wf_primary_misses).  A miss is resolved here -- its zero row stored -- and false
+// returned; else what a lane needs to trace the unit's path: d = normalize(d0), the RNG key and the word
+// of slot field 7 (idx | smp << 32; idx < 2^32: work-list index or pixel).  Both refill paths of k_seg
+// call it: the one statement of a unit's ray.  The STATS counters count where a unit is made.
+struct SegRay {
+    V3 d;
+    uint64_t key, is;
+};
+__device__ __forceinline__ bool seg_make_unit(const DevScene& sc, const CamDev& cam, const TileMap& m, const WFArgs& a, int spp,
+                                              uint64_t seed, double* rgb, uint8_t* rgb8, unsigned long long u, SegRay& r,
+                                              uint32_t& nrays, uint32_t& nres, uint32_t& npx) {
+    unsigned li, smp;
+    if (u < (1ull << 32)) {   // 32-bit division where it suffices
+        li = (unsigned)u / a.ns;
+        smp = a.s0 + ((unsigned)u - li * a.ns);
+    } else {
+        li = (unsigned)(u / (unsigned long long)a.ns);
+        smp = a.s0 + (unsigned)(u - (unsigned long long)li * (unsigned long long)a.ns);
+    }
+    const unsigned ps = a.list[li];   // (prefetching a run's entries into lanes: +3%, round 4)
+    long long idx = -1;
+    const V3 d0 = wf_primary(cam, m, ps, spp, seed, li, smp, idx, r.key);
+    if (smp == 0) ++npx;
+    if (wf_primary_misses(sc, cam, d0)) {
+        ++nrays;
+        ++nres;
+        wf_store(a.part, rgb, rgb8, spp, idx, smp, v3(0, 0, 0));
+        return false;
+    }
+    r.d = normalize(d0);
+    r.is = (uint64_t)(uint32_t)idx | ((uint64_t)smp << 32);
+    return true;
+}
+// this lane's rank among the lanes of a wave mask: the mask's bits below the lane (mbcnt: no lane mask
+// held in two VGPRs -- every k_seg variant came out two VGPRs lower)
+__device__ __forceinline__ unsigned seg_rank(unsigned long long mask) {
+    return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+}
+// a 64-bit value of lane 0 as a wave-uniform one (scalar registers)
+__device__ __forceinline__ unsigned long long seg_uniform64(unsigned long long v) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+// RING (launches with XF_SEG_RING: the host's choice per scene, gi_kernels.hip x_launch_config): lanes
+// without a path take prepared primary rays from the wave's ring, generated a batch of 64 units at a
+// time by all 64 lanes.  Without it they make their units themselves, under the need
+// mask.  The launch's dynamic LDS carries kSegRingBytes behind the path slots only with RING.  (A
+// template parameter: as a run-time choice in one kernel the Cornell box's variant took 12 B of scratch.)
+template <bool STATS, bool LDS, bool W4, bool SH, bool TRI, bool CN, bool FLAT, bool RING>
 __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_WAVES) void k_seg(
     DevScene sc, CamDev cam, V3 light, TileMap m, int spp, int depth, uint64_t seed, double* rgb, uint8_t* rgb8,
     unsigned long long* stats, WFArgs a, int xflags) {
@@ -768,14 +832,26 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
     const unsigned long long n_waves = (unsigned long long)gridDim.x * (blockDim.x >> 6);
     const unsigned long long run = 64ull * (unsigned long long)max(1ll, min(kTake, (long long)(total / (64ull * 8ull * n_waves))));
     uint32_t nnode = 0, nprim = 0, nrays = 0, nres = 0, npx = 0;
-    unsigned long long cur = 0, cur_end = 0;   // the wave's unhanded units [cur, cur_end) (uniform)
-    bool exhausted = false;                    // the frame's units are all handed out (uniform)
-    bool live = false;                         // this lane carries a path
-    unsigned li = 0, smp = 0;
-    long long idx = -1;
-    uint64_t key = 0;
+    SegUnits su;         // the wave's units and its ring's fill (gi_seg_ring.h; uniform)
+    bool live = false;   // this lane carries a path
     V3 o = cam.pos, d = v3(1, 0, 0), L = v3(0, 0, 0), T = v3(1, 1, 1);
-    int splane = 254;   // the own-plane skip of the lane's next ray (254: none; primary rays)
+    int splane = 254;   // the own-plane skip of the lane's next ray (254: none; primary rays) | bounce << kSegPlaneBits
+    // the wave's ring: plane f of entry j at rq[f * 64 + j] (behind the workgroup's path slots)
+    uint64_t* const rq = reinterpret_cast<uint64_t*>(v.pl - threadIdx.x + kWfSlotBytes / sizeof(double)) +
+                         (threadIdx.x >> 6) * (kSegRingPlanes * kSegBatch);
+    // a lane's path begins: the ray and the slot of bounce 0
+    auto begin_path = [&](const V3& dir, uint64_t key, uint64_t is) {
+        live = true;
+        o = cam.pos;
+        d = dir;
+        splane = 254;
+        L = v3(0, 0, 0);
+        T = v3(1, 1, 1);
+        v.pl[0] = 0.0; v.pl[256] = 0.0; v.pl[512] = 0.0;
+        v.pl[768] = 1.0; v.pl[1024] = 1.0; v.pl[1280] = 1.0;
+        slot_put_u64(v.pl, 6, key);
+        slot_put_u64(v.pl, 7, is);
+    };
     // (gi_build.cpp assign_plane_groups: the bound on |d . n| above which a surface's own plane is skipped)
     const double skip_cos = x_skip_cos(sc, cam.pos);
     const float far_r = ray_far_r(sc, cam.pos);   // (far cameras: gi_dev.h ray_org32)
@@ -787,71 +863,86 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
         // ---- lanes without a path take units (primary rays; background samples resolved here)
         for (int burst = 0; burst < GI_SEG_BURST; ++burst) {
             const unsigned long long m_need = __ballot(!live);
-            if (m_need == 0 || (exhausted && cur >= cur_end)) break;
-            const unsigned rank = (unsigned)__popcll(m_need & ((1ull << lane) - 1));
+            if (m_need == 0 || su.done()) break;
+            const unsigned rank = seg_rank(m_need);
             const unsigned n_need = (unsigned)__popcll(m_need);
+            if constexpr (RING) {
+                if (su.wants_batch(n_need)) {   // the ring is empty: all 64 lanes make the run's next batch
+                    if (su.wants_run()) {
+                        unsigned long long nb = 0;
+                        if (lane == 0) nb = atomicAdd(reinterpret_cast<unsigned long long*>(a.take), run);
+                        su.give_run(seg_uniform64(nb), run, total);
+                    }
+                    unsigned long long first = 0;
+                    const unsigned n_batch = su.take_batch(first);
+                    if (n_batch != 0) {
+                        // (the ring is the wave's own: no workgroup barrier, whose waves are in different
+                        // iterations.  The wave's lanes run in lockstep and its LDS operations complete in
+                        // order; the fences keep the compiler from moving the ring's writes over the
+                        // earlier pops' reads, and the pops' reads over the writes)
+                        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                        __builtin_amdgcn_wave_barrier();
+                        SegRay r{};
+                        bool hit = false;
+                        if ((unsigned)lane < n_batch) hit = seg_make_unit(sc, cam, m, a, spp, seed, rgb, rgb8, first + (unsigned)lane, r, nrays, nres, npx);
+                        const unsigned long long m_hit = __ballot(hit);
+                        if (hit) {   // entries in lane order of the hits: j < 64
+                            uint64_t* e = rq + seg_rank(m_hit);
+                            e[0] = (uint64_t)__double_as_longlong(r.d.x);
+                            e[kSegBatch] = (uint64_t)__double_as_longlong(r.d.y);
+                            e[2 * kSegBatch] = (uint64_t)__double_as_longlong(r.d.z);
+                            e[3 * kSegBatch] = r.key;
+                            e[4 * kSegBatch] = r.is;
+                        }
+                        su.push((unsigned)__popcll(m_hit));
+                        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                        __builtin_amdgcn_wave_barrier();
+                    }
+                }
+                // lanes without a path take entries by their rank among such lanes
+                unsigned first_e = 0;
+                const unsigned k = su.pop(n_need, first_e);
+                if (!live && rank < k) {   // first_e + rank < 64: the popped entries were pushed
+                    const uint64_t* e = rq + (first_e + rank);
+                    begin_path(v3(__longlong_as_double((long long)e[0]), __longlong_as_double((long long)e[kSegBatch]),
+                                  __longlong_as_double((long long)e[2 * kSegBatch])),
+                               e[3 * kSegBatch], e[4 * kSegBatch]);
+                }
+                continue;
+            }
+            // ---- the direct path: the lanes make their own units, under the need mask
             unsigned long long u = ~0ull;
-            const unsigned long long avail = cur_end - cur;
-            if (n_need > avail && !exhausted) {   // a new run of units for the lanes beyond it
+            const unsigned long long avail = su.cur_end - su.cur;
+            if (n_need > avail && !su.exhausted) {   // a new run of units for the lanes beyond it
                 unsigned long long nb = 0;
                 if (lane == 0) nb = atomicAdd(reinterpret_cast<unsigned long long*>(a.take), run);
-                nb = __shfl(nb, 0);
+                nb = seg_uniform64(nb);
                 if (nb >= total) {
-                    exhausted = true;
-                    if (!live && rank < avail) u = cur + rank;
-                    cur = cur_end;
+                    su.exhausted = true;
+                    if (!live && rank < avail) u = su.cur + rank;
+                    su.cur = su.cur_end;
                 } else {
                     const unsigned long long ne = min(total, nb + run);
                     if (!live) {
-                        if (rank < avail) u = cur + rank;
+                        if (rank < avail) u = su.cur + rank;
                         else if (nb + (rank - avail) < ne) u = nb + (rank - avail);
                     }
-                    cur = min(ne, nb + (n_need - avail));
-                    cur_end = ne;
-                    if (ne == total) exhausted = true;
+                    su.cur = min(ne, nb + (n_need - avail));
+                    su.cur_end = ne;
+                    if (ne == total) su.exhausted = true;
                 }
             } else {
-                if (!live && rank < avail) u = cur + rank;
-                cur += min((unsigned long long)n_need, avail);
-            }
-            unsigned li_u = 0, smp_u = 0;
-            if (u != ~0ull) {
-                if (u < (1ull << 32)) {
-                    li_u = (unsigned)u / a.ns;
-                    smp_u = a.s0 + ((unsigned)u - li_u * a.ns);
-                } else {
-                    li_u = (unsigned)(u / (unsigned long long)a.ns);
-                    smp_u = a.s0 + (unsigned)(u - (unsigned long long)li_u * (unsigned long long)a.ns);
-                }
+                if (!live && rank < avail) u = su.cur + rank;
+                su.cur += min((unsigned long long)n_need, avail);
             }
             if (!live && u != ~0ull) {
-                li = li_u;
-                smp = smp_u;
-                const unsigned ps = a.list[li];   // (prefetching a run's entries into lanes: +3%, round 4)
-                const V3 d0 = wf_primary(cam, m, ps, spp, seed, li, smp, idx, key);
-                if (smp == 0) ++npx;
-                if (wf_primary_misses(sc, cam, d0)) {
-                    ++nrays;
-                    ++nres;
-                    wf_store(a.part, rgb, rgb8, spp, idx, smp, v3(0, 0, 0));
-                } else {
-                    live = true;
-                    o = cam.pos;
-                    d = normalize(d0);
-                    splane = 254;
-                    L = v3(0, 0, 0);
-                    T = v3(1, 1, 1);
-                    v.pl[0] = 0.0; v.pl[256] = 0.0; v.pl[512] = 0.0;
-                    v.pl[768] = 1.0; v.pl[1024] = 1.0; v.pl[1280] = 1.0;
-                    slot_put_u64(v.pl, 6, key);
-                    slot_put_u64(v.pl, 7, (uint64_t)(uint32_t)idx | ((uint64_t)smp << 32));   // (idx < 2^32: work-list index or pixel)
-                    slot_put_u64(v.pl, 8, 0ull);
-                }
+                SegRay r{};
+                if (seg_make_unit(sc, cam, m, a, spp, seed, rgb, rgb8, u, r, nrays, nres, npx)) begin_path(r.d, r.key, r.is);
             }
         }
         if (STATS) ws.cyc_ref += clock64() - t_ref;
         if (__ballot(live) == 0) {
-            if (exhausted && cur >= cur_end) break;
+            if (su.done()) break;
             continue;
         }
         // ---- one segment of every live path
@@ -861,11 +952,11 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
         }
         const bool cont = x_segment<STATS, LDS, SH, TRI, CN, FLAT>(
             sc, v, light, depth, no_shadow, live,
-            [&] { return PathId{slot_get_u64(v.pl, 6), (unsigned)(slot_get_u64(v.pl, 7) >> 32), (int)slot_get_u64(v.pl, 8)}; },
+            [&] { return PathId{slot_get_u64(v.pl, 6), (unsigned)(slot_get_u64(v.pl, 7) >> 32), splane >> kSegPlaneBits}; },
             o, d, L, T, nnode, nprim, nrays, ws, skip_cos, &splane, far_r);
         if (live) {
             if (cont) {
-                slot_put_u64(v.pl, 8, slot_get_u64(v.pl, 8) + 1);
+                splane += 1 << kSegPlaneBits;   // the next bounce
             } else {
                 const uint64_t is = slot_get_u64(v.pl, 7);
                 wf_store(a.part, rgb, rgb8, spp, (long long)(uint32_t)is, (unsigned)(is >> 32), L);
@@ -1146,8 +1237,14 @@ size_t wf_slot_bytes() { return kWfSlotBytes; }
 // the scene's share of that LDS (LDS-resident scenes): the staged records (entity records included:
 // read from global memory by the shading instead, C3 4.65 -> 4.69 ms, and 5 waves per SIMD with them
 // there, 96 VGPRs and 120 B of scratch, 4.79 ms; profiles/r06_ab.txt)
-// (and, where the flat leaf query applies, its per-leaf candidate words)
-size_t wf_scene_lds_bytes(const DevScene& sc) { return (size_t)sc.x_lds_bytes + (sc.x_flat ? kFlatPkBytes : 0); }
+// (and, where the flat leaf table applies, its per-leaf candidate words).  flat: the launch runs the flat
+// kernels, which do not stage the wide nodes (wf_stage)
+size_t wf_scene_lds_bytes(const DevScene& sc, bool flat) {
+    const size_t nodes = (flat && sc.x_flat) ? (size_t)sc.n_xwnodes * sizeof(XWNode) : 0;
+    return (size_t)sc.x_lds_bytes - nodes + (sc.x_flat ? kFlatPkBytes : 0);
+}
+// dynamic LDS of a k_seg launch that runs the ring (XF_SEG_RING), beyond the other kernels' bytes
+size_t wf_seg_ring_bytes() { return kSegRingBytes; }
 
 // The kernel variant for a scene: f(XTag) (var: XLaunchCfg::var; flat: the flat leaf query, LDS-resident
 // scenes whose table applies -- DevScene::x_flat -- unless GI_X_FLAT=0).  TRI of an LDS-resident scene is
@@ -1163,8 +1260,8 @@ void wf_dispatch(const DevScene& sc, XVariant var, bool flat, bool stats, F&& f)
         with_bools([&](auto S, auto T, auto C) { f(XTag<S.value, false, false, false, T.value, C.value, false>{}); },
                    stats, sc.x_tri_only != 0, sc.xcnodes != nullptr);
 }
-template <typename V>
-constexpr auto seg_kernel(V) { return &k_seg<V::stats, V::lds, V::w4, V::sh, V::tri, V::cn, V::flat>; }
+template <bool RING, typename V>
+constexpr auto seg_kernel(V) { return &k_seg<V::stats, V::lds, V::w4, V::sh, V::tri, V::cn, V::flat, RING>; }
 template <typename V>
 constexpr auto bounce_kernel(V) { return &k_wf_bounce<V::stats, V::lds, V::w4, V::sh, V::tri, V::cn, V::flat>; }
 
@@ -1174,7 +1271,7 @@ constexpr auto cast_kernel(V) { return &k_cast<ANY, V::lds, V::w4, V::sh, V::tri
 template <typename V>
 constexpr auto aov_kernel(V) { return &k_aov<V::lds, V::w4, V::sh, V::tri, V::cn, V::flat>; }
 
-// resident workgroups per CU of the kernel a form (1: k_wf_bounce, 2: k_seg; the ray queries: 3 k_cast
+// resident workgroups per CU of the kernel a form (1: k_wf_bounce, 2: k_seg, 6: k_seg with the ring; the ray queries: 3 k_cast
 // closest hit, 4 k_cast any hit; 5: the feature buffers, k_aov) runs for this scene
 hipError_t wf_occupancy(const DevScene& sc, XVariant var, bool flat, size_t lds_bytes, int form, int* per_cu) {
     hipError_t e = hipSuccess;
@@ -1182,7 +1279,8 @@ hipError_t wf_occupancy(const DevScene& sc, XVariant var, bool flat, size_t lds_
         const void* f = form == 5   ? reinterpret_cast<const void*>(aov_kernel(V))
                         : form == 4 ? reinterpret_cast<const void*>(cast_kernel<true>(V))
                         : form == 3 ? reinterpret_cast<const void*>(cast_kernel<false>(V))
-                        : form == 2 ? reinterpret_cast<const void*>(seg_kernel(V))
+                        : form == 6 ? reinterpret_cast<const void*>(seg_kernel<true>(V))
+                        : form == 2 ? reinterpret_cast<const void*>(seg_kernel<false>(V))
                                     : reinterpret_cast<const void*>(bounce_kernel(V));
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, f, 256, lds_bytes);
     });
@@ -1214,7 +1312,10 @@ hipError_t launch_wf(const DevScene& sc, XVariant var, size_t lds_bytes, int res
         a.ns = (unsigned)(s1 - s0);
         if (ev_begin) (void)hipEventRecord(ev_begin, stream);
         wf_dispatch(sc, var, flat, stats != nullptr, [&](auto V) {
-            hipLaunchKernelGGL(seg_kernel(V), grid, block, lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, rgb, rgb8, stats, a, xflags);
+            if (xflags & XF_SEG_RING)   // (lds_bytes then holds the ring's: XLaunchCfg::seg_lds_bytes)
+                hipLaunchKernelGGL(seg_kernel<true>(V), grid, block, lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, rgb, rgb8, stats, a, xflags);
+            else
+                hipLaunchKernelGGL(seg_kernel<false>(V), grid, block, lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, rgb, rgb8, stats, a, xflags);
         });
         if (ev_end) (void)hipEventRecord(ev_end, stream);
         return hipGetLastError();

@@ -25,6 +25,7 @@
  *   gi_unshard_device    reassembles a frame from per-rank packed tiles after the RCCL gather
  *   gi_scene_kernel_ms   HIP-event duration of the last timed render's dominant kernel (bench)
  *   gi_scene_x_form      which Mode X form (persistent kernel / wavefront) a render would run
+ *   gi_scene_seg_ring    whether that form would refill its lanes from the per-wave ring of primary rays
  *   gi_kat_*             known-answer TEST hooks: the device's ExpBox node test and the Mode X
  *                        queries ray by ray (gi_kat_x_query, gi_kat_x_variant)
  *   gi_octree_*          Octree(min,max) + push_back (octree.h:14-43) and the public query
@@ -52,7 +53,7 @@
 extern "C" {
 #endif
 
-#define GI_ABI_VERSION 13
+#define GI_ABI_VERSION 14
 
 typedef enum gi_status {
     GI_OK = 0,
@@ -372,6 +373,12 @@ int gi_scene_kernel_ms(gi_scene* scene, float* avg_ms, int64_t* n);
  * path-state kernel k_mode_x, 1 = the wavefront form (k_wf_bounce once per bounce), 2 = the
  * segment-synchronous form (k_seg); Mode R: 0. */
 int gi_scene_x_form(gi_scene* scene, const gi_opts* opts, int32_t* form);
+/* Whether a render of `scene` with `opts` would refill k_seg's lanes from its per-wave ring of
+ * prepared primary rays (ABI 14; bench labels, tests): 1 = the segment-synchronous form with the
+ * ring -- chosen per scene where the ring's LDS does not lower the kernel's resident workgroups, unless
+ * GI_SEG_RING=0 is set in the environment; 0 = k_seg's lanes make their own units, or another form
+ * or mode runs.  Frames are the same bit for bit either way. */
+int gi_scene_seg_ring(gi_scene* scene, const gi_opts* opts, int32_t* on);
 /* Mode R kernel a render of `scene` with `opts` would run (ABI 10; bench labels, tests): 0 = k_mode_r
  * (one lane per pixel: small scenes, GI_FLAG_R_DFS), 1 = the flat phases (k_rf_walk, k_rf_hit,
  * k_rf_scan, k_rf_reach, k_rf_shade; scenes of more than 4096 entities; their overflowed tiles by
