@@ -66,7 +66,7 @@ STAT_X_IT_RS, STAT_X_LN_RS, STAT_X_IT_ST, STAT_X_LN_ST = 20, 21, 22, 23
 STAT_R_PAIRS, STAT_R_OVF_TILES = 24, 25
 STATS_N = 26
 TILE = 8
-ABI_VERSION = 14
+ABI_VERSION = 15
 RAY_DOUBLES = 8   # a ray record of the batched queries: o[3], d[3], tmax, reserved (gi.h GI_RAY_DOUBLES)
 # the feature buffers of DeviceScene.render_aov (gi.h gi_aov, in its field order): name -> (dtype, trailing shape)
 AOV_OUTPUTS = ("t", "normal", "albedo", "prim", "entity", "uv")
@@ -129,7 +129,7 @@ TILE_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ct
 
 EXPORTS = ["gi_abi_version", "gi_last_error", "gi_camera_init", "gi_scene_create", "gi_scene_destroy",
            "gi_scene_get_info", "gi_render", "gi_render_device", "gi_shard_tiles", "gi_unshard_device",
-           "gi_trace_ray", "gi_kat_expbox", "gi_kat_x_query", "gi_kat_x_variant", "gi_scene_kernel_ms", "gi_scene_x_form", "gi_scene_seg_ring", "gi_scene_r_kernel", "gi_octree_create", "gi_octree_destroy",
+           "gi_trace_ray", "gi_kat_expbox", "gi_kat_x_query", "gi_kat_x_variant", "gi_kat_x_texel", "gi_scene_kernel_ms", "gi_scene_x_form", "gi_scene_seg_ring", "gi_scene_r_kernel", "gi_octree_create", "gi_octree_destroy",
            "gi_octree_intersect", "gi_multi_create", "gi_multi_destroy", "gi_multi_info", "gi_multi_render", "gi_device_count",
            "gi_device_list", "gi_build_id", "gi_obj_parse", "gi_intersect", "gi_occluded", "gi_intersect_device",
            "gi_occluded_device", "gi_render_aov", "gi_render_aov_device", "gi_camera_rays", "gi_camera_rays_device"]
@@ -171,6 +171,7 @@ def lib():
         ip = ctypes.POINTER(ctypes.c_int32)
         L.gi_kat_x_query.argtypes = [vp, i32, dp, dp, i32, ip, dp, ip, ip, ip, dp, ip, dp]
         L.gi_kat_x_variant.argtypes = [vp, i32, ip]
+        L.gi_kat_x_texel.argtypes = [vp, i32, dp, i32, dp, ip]
         i64 = ctypes.c_int64
         L.gi_intersect.argtypes = [vp, i64, dp, dp, ip, ip, dp]
         L.gi_occluded.argtypes = [vp, i64, dp, ip]
@@ -686,6 +687,22 @@ class DeviceScene:
                                     out["skip2"].ctypes.data_as(ip), ctypes.byref(sc)), "gi_kat_x_query")
         out["skip_cos"] = sc.value if n else None
         return out
+
+    def kat_x_texel(self, ents, points, exact: bool = False):
+        """The texel Mode X's segment kernels shade a hit with (gi_kat_x_texel; a test hook): entity
+        indices (n) and points (n, 3) -> (texel (n, 3) float64, how (n) int32).  exact=False runs the
+        shading helper (how: 1 its fp32 filter decided, 2 the exact code, 0 a triangle of truncated
+        colour (1, 1, 1)), exact=True the exact texture-coordinate code alone (how: 2)."""
+        pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+        n = pts.shape[0]
+        recs = np.empty((n, 4), np.float64)
+        recs[:, 0] = np.asarray(ents, np.float64).reshape(n)
+        recs[:, 1:] = pts
+        tex, how = np.zeros((n, 3)), np.zeros(n, np.int32)
+        ip, dp = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)
+        _check(lib().gi_kat_x_texel(self._h, n, recs.ctypes.data_as(dp), 1 if exact else 0, tex.ctypes.data_as(dp),
+                                    how.ctypes.data_as(ip)), "gi_kat_x_texel")
+        return tex, how
 
 
 _scratch = None

@@ -40,6 +40,8 @@ hipError_t launch_box_kat(int n, const double* recs, int32_t* out, hipStream_t s
 hipError_t launch_x_query(const DevScene& sc, const XLaunchCfg& xc, V3 cam_pos, int flags, int n, const double* recs,
                           int32_t* oi, double* od, hipStream_t stream);
 void x_query_variant(const DevScene& sc, const XLaunchCfg& xc, int flags, int32_t out[6]);
+hipError_t launch_x_texel_kat(const DevScene& sc, XVariant var, int n, int mode, const double* recs, int32_t* oi, double* od,
+                              hipStream_t stream);
 hipError_t launch_ray_query(const DevScene& sc, const XLaunchCfg& xc, bool any, const CastIO& io, hipStream_t stream);
 hipError_t launch_aov(const DevScene& sc, const XLaunchCfg& xc, const CamDev& cam, const AovIO& io, hipStream_t stream);
 hipError_t launch_cam_rays(const CamDev& cam, int x0, int y0, int cols, int rows, double* rays, hipStream_t stream);
@@ -1114,6 +1116,37 @@ int gi_kat_x_variant(gi_scene* s, int flags, int32_t out[6]) {
         std::lock_guard<std::mutex> lk(s->mu);
         x_query_variant(s->dev, s->xcfg, flags, out);
         return GI_OK;
+    });
+}
+
+int gi_kat_x_texel(gi_scene* s, int n, const double* recs, int mode, double* texel, int32_t* how) {
+    return guard([&]() -> int {
+        DeviceRestore keep;   // the caller's current device, restored on return
+        if (!s || n < 0 || (mode != 0 && mode != 1)) return fail(GI_ERR_ARG, "bad arguments");
+        if (n > 0 && (!recs || !texel || !how)) return fail(GI_ERR_ARG, "null argument");
+        if (n == 0) return GI_OK;
+        std::lock_guard<std::mutex> lk(s->mu);
+        for (size_t i = 0; i < (size_t)n; ++i) {   // (the kernel indexes the entity array with it)
+            const double ent = recs[4 * i];
+            if (!(ent >= 0.0 && ent < (double)s->dev.n_ents && ent == (double)(int32_t)ent))
+                return fail(GI_ERR_ARG, "entity index out of range");
+        }
+        int rc = bind_device(s->device);
+        if (rc) return rc;
+        double *d_r = nullptr, *d_d = nullptr;
+        int32_t* d_i = nullptr;
+        hipError_t e;
+        if ((e = hipMalloc((void**)&d_r, (size_t)n * 4 * sizeof(double))) == hipSuccess &&
+            (e = hipMalloc((void**)&d_i, (size_t)n * sizeof(int32_t))) == hipSuccess)
+            e = hipMalloc((void**)&d_d, (size_t)n * 3 * sizeof(double));
+        if (e == hipSuccess) e = hipMemcpy(d_r, recs, (size_t)n * 4 * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = launch_x_texel_kat(s->dev, s->xcfg.var, n, mode, d_r, d_i, d_d, nullptr);
+        if (e == hipSuccess) e = hipMemcpy(how, d_i, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(texel, d_d, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost);
+        (void)hipFree(d_r);
+        (void)hipFree(d_i);
+        (void)hipFree(d_d);
+        return e == hipSuccess ? GI_OK : hip_fail(e, "gi_kat_x_texel");
     });
 }
 

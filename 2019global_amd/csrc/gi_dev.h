@@ -463,12 +463,7 @@ template <bool TRI = false>
 __device__ __forceinline__ void x_texcoord(const DevScene& sc, const REnt& e, V3 ip, int32_t& x, int32_t& y) {
     if (TRI) {
         if (e.kind == K_IMP_TRIANGLE) {
-            const V3 p1 = ld3(e.qv0), p21 = ld3(e.qv1), i1 = ip - p1;
-            const double i1l = gsqrt(sq3(i1));
-            const double c = dot(p21, i1) / (e.qv2[0] * i1l);
-            const double ixl = i1l * mx_sin_acos(c);
-            y = x86_trunc(i1l / e.qv2[2]);
-            x = x86_trunc(ixl / e.qv2[1]);
+            tri_texcoord(e.qv0, e.qv1, e.qv2, ip, x, y);
         } else if (e.kind == K_EXP_QUAD || e.kind == K_EXP_CUBE) {
             const bool q = e.kind == K_EXP_QUAD;
             const double uv = (double)e.width / 160.0, uh = (double)e.length / 160.0;
@@ -495,12 +490,7 @@ __device__ __forceinline__ void x_texcoord(const DevScene& sc, const REnt& e, V3
         const double unit_h = 2.0 * REF_PI * small_r / 320.0;
         x = x86_trunc(small_r * mx_acos(ch) / unit_h);
     } else if (e.kind == K_IMP_TRIANGLE) {
-        const V3 p1 = ld3(e.qv0), p21 = ld3(e.qv1), i1 = ip - p1;
-        const double i1l = gsqrt(sq3(i1));
-        const double c = dot(p21, i1) / (e.qv2[0] * i1l);
-        const double ixl = i1l * mx_sin_acos(c);
-        y = x86_trunc(i1l / e.qv2[2]);
-        x = x86_trunc(ixl / e.qv2[1]);
+        tri_texcoord(e.qv0, e.qv1, e.qv2, ip, x, y);
     } else if (e.kind == K_EXP_QUAD) {
         const double uv = (double)e.width / 160.0, uh = (double)e.length / 160.0;
         const V3 rv = ld3(e.qv0) - ld3(e.qv1), i1 = ip - ld3(e.qv1);
@@ -551,6 +541,39 @@ __device__ __forceinline__ void x_texcoord(const DevScene& sc, const REnt& e, V3
         x = 0;
         y = 0;
     }
+}
+
+// texel(e.color, x_texcoord<TRI>(e, ip)) for shading, which needs the colour and not the coordinates.
+// A triangle's lane takes tri_texel_fast's answer (gi_math.h: a colour that truncates to (1, 1, 1), or
+// the fp32 filter where it is sure); only if some lane of the wave is left -- a triangle the filter
+// will not decide, or an entity of another kind -- does the wave run the exact code, for those lanes.
+// Every lane's value is the exact code's.  *how (may be null; the known-answer hook): 1 the filter
+// decided this lane, 2 the lane asked for the exact code, 0 neither (the colour decided).
+// The TRI kernels only: in the others (waves that mix triangles with the acos-mapped kinds) the filter
+// was measured and did not pay (X-main +0.1%, X-zoo +0.6%: DESIGN.md §9 round 10), so they run the
+// exact code for every lane, as before.
+template <bool TRI = false>
+__device__ __forceinline__ V3 x_texel(const DevScene& sc, const REnt& e, V3 ip, int* how = nullptr) {
+    if (!TRI) {
+        int32_t tu, tv;
+        x_texcoord<TRI>(sc, e, ip, tu, tv);
+        if (how) *how = 2;
+        return texel(ld3(e.color), tu, tv);
+    }
+    // (one flag, not the colour, is live across the exact code; the filter under the kind's branch, not
+    // evaluated for every lane and masked: that form cost k_wf_bounce<0,1,1,0,1,0,0> 4 B of scratch and
+    // the 3-wave kernels 4-5 VGPRs, this one leaves every timed kernel's registers and scratch alone)
+    bool white = false, flt = false, need = true;
+    if (e.kind == K_IMP_TRIANGLE) need = !tri_texel_fast(ld3(e.color), ld3(e.qv0), ld3(e.qv1), e.qv2[1], e.qv2[2], ip, white, &flt);
+    if (how) *how = need ? 2 : (flt ? 1 : 0);
+    if (__builtin_amdgcn_ballot_w64(need) != 0) {
+        if (need) {
+            int32_t tu, tv;
+            x_texcoord<TRI>(sc, e, ip, tu, tv);
+            white = texel_white(tu, tv);
+        }
+    }
+    return texel_pick(ld3(e.color), white);
 }
 
 }  // namespace

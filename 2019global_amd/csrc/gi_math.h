@@ -392,16 +392,126 @@ GI_HD void mx_disk(double u1, double u2, double& dx, double& dy, double& r2) {
     r2 = zero ? 0.0 : r * r;
 }
 
-GI_HD V3 texel(V3 color, int32_t u, int32_t v) {
+GI_HD bool texel_white(int32_t u, int32_t v) {
     // pattern[u % 32][v % 32] with C remainders: the compiled reference reads the FLAT element
     // (u%32)*32 + v%32 of the 32x32 array; inside [0,1024) that is exact, outside it reads stack
     // memory (UB, no parity claim) and this path wraps the flat index into the array (oracle: same).
     int f = (u % 32) * 32 + (v % 32);
     if (f < 0 || f >= 1024) f = ((f % 1024) + 1024) % 1024;
     const int i = f >> 5, j = f & 31;
-    const bool white = ((i <= 16) & (j <= 16)) | ((i > 16) & (j > 16));   // (a select, not a branch)
+    return ((i <= 16) & (j <= 16)) | ((i > 16) & (j > 16));
+}
+GI_HD V3 texel_pick(V3 color, bool white) {
     const V3 c = v3((double)x86_trunc(color.x), (double)x86_trunc(color.y), (double)x86_trunc(color.z));
-    return white ? v3(1, 1, 1) : c;
+    return white ? v3(1, 1, 1) : c;   // (a select, not a branch)
+}
+GI_HD V3 texel(V3 color, int32_t u, int32_t v) { return texel_pick(color, texel_white(u, v)); }
+
+// ImpTriangle::getTextureCoord (entities.h:277-303) with the per-triangle constants of the entity's
+// frame (REnt; gi_build.cpp): qv0 = p1, qv1 = p21 = p2 - p1, qv2 = (|p21|, unit_v, unit_h).  x = u, y = v.
+GI_HD void tri_texcoord(const double* qv0, const double* qv1, const double* qv2, V3 ip, int32_t& x, int32_t& y) {
+    const V3 p1 = ld3(qv0), p21 = ld3(qv1), i1 = ip - p1;
+    const double i1l = gsqrt(sq3(i1));
+    const double c = dot(p21, i1) / (qv2[0] * i1l);
+    const double ixl = i1l * mx_sin_acos(c);
+    y = x86_trunc(i1l / qv2[2]);
+    x = x86_trunc(ixl / qv2[1]);
+}
+
+// ---- fp32 filter in front of tri_texcoord + texel (DESIGN.md §5 "The checker texel") -------------
+// texel() reduces the two coordinates to one boolean: white iff the classes of u mod 32 and v mod 32
+// (<= 16 or > 16) agree.  For u, v >= 0 the class of trunc(u) mod 32 is that of the real value's
+// residue u mod 32 against [0, 17) / [17, 32): it changes at the residues 0, 17 and 32 only.
+// tri_tex_class estimates both coordinates in fp32 and answers only where each residue is farther
+// from 0, 17 and 32 than a margin of 8 times the estimate's error bound; everything else is left to
+// the exact code, so the result never depends on the estimate.
+//
+// Error bound, e = 2^-24 (fp32 unit roundoff), a = fl32(P - p1), q = fl32(p21) (P - p1 is formed in
+// fp64 first -- the very vector the exact code uses -- so the conversion error is relative to |P - p1|,
+// not to |P|), S = |a| / unit_v (the value u takes at a right angle to the edge; u <= S):
+//   v^ = |a| / unit_h:   the squared length 2e (conversions) + 3e (sum of three squares), halved by the
+//       root: 2.5e; root 2e (1 ulp, hardware); unit_h's conversion e, reciprocal 2e (1 ulp), product e:
+//       8.5e.  The exact code's own v is within 1e-15 of the true value.          |v^ - v| <= 10e v
+//   u^ = |q x a| / (|q| unit_v):  each component of the cross product has the absolute error
+//       4e (|q_i a_j| + |q_j a_i|) (2e from the conversions, 2e from its own three roundings), as a
+//       vector at most 4 sqrt(2) e |q||a| = 5.7e |q||a|; its length 1.5e + 2e = 3.5e more (of |q x a|
+//       <= |q||a|); a squared length that underflows is below 2^-63 against |q||a| > 2^-40: 2e; the
+//       divisor |q| unit_v: 5.5e + e + e, its reciprocal 2e, the last product e: 10.5e.  Sum 21.7e S.
+//       The exact code's u against the true value: its c is the cosine to 10 u64 (dot product 3,
+//       lengths 2.5 each, product, quotient), 1 - c^2 is sin^2 to 22 u64 absolutely, and
+//       |sqrt(s + h) - sqrt(s)| <= sqrt(|h|), so its sine is off by at most sqrt(22 * 2^-53) = 0.83e:
+//       ill-conditioned only near the p1 -> p2 edge, where u is small (the cross-product form has no
+//       cancellation there).                                                       |u^ - u| <= 24e S
+// Margins: 2^-16 v^ = 256e v^ for v (bound 10e) and 2^-16 S^ = 256e S^ for u (bound 24e; S^ is S to
+// 8.5e): more than 8 times the bound each (80e, 192e), the rest covers the rounding of 17 -/+ margin
+// and 32 - margin (at most 2^-20, where the margin is at least 2^-12 because S >= u >= 16).  The
+// residue itself is exact in fp32: a value below 2^20 times 1/32, its fract, times 32.
+// Where the exact code's 1 - c^2 is negative (u = INT_MIN, class 0) the true sine is below 0.83e, u^
+// is below the margin: not sure.  P == p1: v^ = 0, not sure.  NaN, infinite, negative, huge values
+// and frames with a zero or out-of-range length or unit fail a comparison: not sure.
+// Device: v_rcp_f32 / v_sqrt_f32 / v_fract_f32 (1 ulp each; every operand is kept in the normal
+// range by the guards); host: IEEE division, sqrt and floor.  The two may disagree on `sure`.
+GI_HD float tc_rcp(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_rcpf(x);
+#else
+    return 1.0f / x;
+#endif
+}
+GI_HD float tc_sqrt(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_sqrtf(x);
+#else
+    return std::sqrt(x);
+#endif
+}
+GI_HD float tc_fract(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_fractf(x);
+#else
+    return x - std::floor(x);
+#endif
+}
+// one coordinate: its residue mod 32 clear of 0, 17 and 32 by the margin m; hi = residue > 17
+GI_HD bool tc_clear(float est, float m, bool& hi) {
+    const float r = 32.0f * tc_fract(est * 0.03125f);
+    hi = r > 17.0f;
+    return (est >= 0.0f) & (est < 0x1p20f) & (((r > m) & (r < 17.0f - m)) | ((r > 17.0f + m) & (r < 32.0f - m)));
+}
+struct TexClass {
+    bool sure;     // the classes below are those of the exact coordinates
+    bool hu, hv;   // u mod 32 > 16, v mod 32 > 16
+};
+GI_HD TexClass tri_tex_class(V3 p1, V3 p21, double unit_v, double unit_h, V3 ip) {
+    const V3 i1 = ip - p1;
+    const float ax = (float)i1.x, ay = (float)i1.y, az = (float)i1.z;
+    const float qx = (float)p21.x, qy = (float)p21.y, qz = (float)p21.z;
+    const float fuv = (float)unit_v, fuh = (float)unit_h;
+    const float sa = ax * ax + ay * ay + az * az, sq = qx * qx + qy * qy + qz * qz;
+    const float nx = qy * az - ay * qz, ny = qz * ax - az * qx, nz = qx * ay - ax * qy;
+    const float sn = nx * nx + ny * ny + nz * nz;
+    const float la = tc_sqrt(sa);
+    const float su = la * tc_rcp(fuv);                          // S^
+    const float ev = la * tc_rcp(fuh);                          // v^
+    const float eu = tc_sqrt(sn) * tc_rcp(tc_sqrt(sq) * fuv);   // u^
+    const float lo = 0x1p-40f, hi = 0x1p40f;
+    const bool ranged = (sa > lo) & (sa < hi) & (sq > lo) & (sq < hi) & (fuv > lo) & (fuv < hi) & (fuh > lo) & (fuh < hi);
+    TexClass r;
+    const bool cu = tc_clear(eu, 0x1p-16f * su, r.hu), cv = tc_clear(ev, 0x1p-16f * ev, r.hv);
+    r.sure = ranged & cu & cv;
+    return r;
+}
+// texel(color, u, v) = texel_pick(color, white) of a triangle's hit point where `white` can be had
+// without the exact coordinates: a truncated colour of (1, 1, 1) gives (1, 1, 1) on either side of the
+// pattern (white = true serves); otherwise texel_white's own rule on the classes where the filter is
+// sure.  false: the exact code decides (tri_texcoord + texel_white).  *filtered (may be null): the
+// filter, not the colour, decided.
+GI_HD bool tri_texel_fast(V3 color, V3 p1, V3 p21, double unit_v, double unit_h, V3 ip, bool& white, bool* filtered = nullptr) {
+    const bool plain = (x86_trunc(color.x) == 1) & (x86_trunc(color.y) == 1) & (x86_trunc(color.z) == 1);
+    const TexClass k = tri_tex_class(p1, p21, unit_v, unit_h, ip);
+    white = plain | (k.hu == k.hv);
+    if (filtered) *filtered = k.sure & !plain;
+    return plain | k.sure;
 }
 
 // Image::setPixel quantisation (image.h:14-16): (int)(255*c); an out-of-range channel makes the

@@ -588,9 +588,7 @@ __device__ __forceinline__ bool x_segment(const DevScene& sc, const WFView& v, c
         V3 N = (TRI || p.kind == 0) ? ld3(p.n) : normalize(P - ld3(p.a));
         N = dot(d, N) < 0 ? N : -N;
         const REnt& e = v.EN[p.ent];
-        int32_t tu, tv;
-        x_texcoord<TRI>(sc, e, P, tu, tv);
-        const V3 tc = texel(ld3(e.color), tu, tv);
+        const V3 tc = x_texel<TRI>(sc, e, P);
         const V3 la = tc * e.shader[0];
         V3 loc = la;
         if (!occl) {
@@ -1036,6 +1034,39 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
     if (i == 0) od[2 * (long long)n] = skip_cos;
 }
 
+// Known-answer hook (gi_kat_x_texel; tests): the texel x_segment shades a hit with, one (entity, point)
+// per lane.  Record i: the entity index (a double holding an integer in [0, n_ents), checked by the
+// host) and the point (4 doubles).  mode 0: x_texel, the helper x_segment calls; mode 1: the exact code
+// it stands for (x_texcoord + texel).  Lanes past n run the helper without a point (entity 0, the
+// origin).  od[3 i ..]: the texel; oi[i]: x_texel's `how` (mode 1: 2).  The entity records are read from
+// global memory (the helper is the same code wherever they lie).
+template <bool TRI>
+__global__ __launch_bounds__(256) void k_x_texel_kat(DevScene sc, int n, int mode, const double* recs, int32_t* oi, double* od) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bool act = i < (long long)n;
+    int ent = 0;
+    V3 P = v3(0, 0, 0);
+    if (act) {
+        const double* q = recs + 4 * i;
+        ent = (int)q[0];
+        P = v3(q[1], q[2], q[3]);
+    }
+    const REnt& e = sc.ents[ent];
+    int how = 2;
+    V3 tc;
+    if (mode == 0) {
+        tc = x_texel<TRI>(sc, e, P, &how);
+    } else {
+        int32_t tu, tv;
+        x_texcoord<TRI>(sc, e, P, tu, tv);
+        tc = texel(ld3(e.color), tu, tv);
+    }
+    if (act) {
+        od[3 * i] = tc.x; od[3 * i + 1] = tc.y; od[3 * i + 2] = tc.z;
+        oi[i] = how;
+    }
+}
+
 // The public ray queries (gi_intersect*, gi_occluded*; DESIGN.md §5 "Ray queries"): the closest hit
 // (ANY = false: the (t, primitive) minimum over t in (MX_TMIN, tmax), with the primitive's entity and
 // the facing unit normal) or any hit (ANY: 1 / 0) of n caller-supplied rays, through x_query in the
@@ -1364,6 +1395,18 @@ hipError_t launch_x_query_kat(const DevScene& sc, XVariant var, bool flat, size_
     wf_dispatch(sc, var, flat, false, [&](auto V) {
         using T = decltype(V);
         hipLaunchKernelGGL((k_x_query_kat<T::lds, T::w4, T::sh, T::tri, T::cn, T::flat>), grid, block, lds_bytes, stream, sc, cam_pos, n, recs, oi, od);
+    });
+    return hipGetLastError();
+}
+
+// gi_kat_x_texel's launch: TRI as k_seg's variant for the scene has it (wf_dispatch), one record per lane
+hipError_t launch_x_texel_kat(const DevScene& sc, XVariant var, int n, int mode, const double* recs, int32_t* oi, double* od,
+                              hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    const dim3 grid((unsigned)(((long long)n + 255) / 256)), block(256);
+    wf_dispatch(sc, var, false, false, [&](auto V) {
+        using T = decltype(V);
+        hipLaunchKernelGGL((k_x_texel_kat<T::tri>), grid, block, 0, stream, sc, n, mode, recs, oi, od);
     });
     return hipGetLastError();
 }

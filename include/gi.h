@@ -27,7 +27,8 @@
  *   gi_scene_x_form      which Mode X form (persistent kernel / wavefront) a render would run
  *   gi_scene_seg_ring    whether that form would refill its lanes from the per-wave ring of primary rays
  *   gi_kat_*             known-answer TEST hooks: the device's ExpBox node test and the Mode X
- *                        queries ray by ray (gi_kat_x_query, gi_kat_x_variant)
+ *                        queries ray by ray (gi_kat_x_query, gi_kat_x_variant), the texel a hit
+ *                        is shaded with (gi_kat_x_texel)
  *   gi_octree_*          Octree(min,max) + push_back (octree.h:14-43) and the public query
  *                        Octree::intersect(const Ray&) (octree.h:46-68 -> Node::intersect :132-155)
  *                        on the host, for reference-side callers of the candidate list
@@ -53,7 +54,7 @@
 extern "C" {
 #endif
 
-#define GI_ABI_VERSION 14
+#define GI_ABI_VERSION 15
 
 typedef enum gi_status {
     GI_OK = 0,
@@ -456,6 +457,15 @@ int gi_kat_x_query(gi_scene* scene, int n, const double* recs, const double cam_
  * in one word: trees of at most 8 levels), TRI (triangles only), CN (quantised nodes), FLAT (the flat
  * leaf table answers the queries). */
 int gi_kat_x_variant(gi_scene* scene, int flags, int32_t out[6]);
+
+/* Known-answer hook (a TEST hook; ABI 15): the texel Mode X's segment kernels shade a hit with.  n host
+ * records of 4 doubles -- the entity's index (push order, an integer in [0, entity count)) and a point
+ * taken as the hit point on it.  mode 0 runs the shading helper itself (an fp32 filter decides the
+ * checker's colour where it is sure, the exact texture-coordinate code everywhere else); mode 1 the
+ * exact code alone.  texel: 3 doubles per record.  how[i]: 1 the filter decided the record, 2 it went
+ * to the exact code, 0 neither was needed (a triangle whose truncated colour is (1, 1, 1)); mode 1: 2.
+ * GI_ERR_ARG for an entity index out of range or another mode.  n = 0 launches nothing. */
+int gi_kat_x_texel(gi_scene* scene, int n, const double* recs, int mode, double* texel, int32_t* how);
 
 #ifdef __cplusplus
 }
