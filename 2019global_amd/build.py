@@ -1,7 +1,8 @@
 """Builds 2019global_amd/libgi.so in-tree (gfx950 only).
 
 Host translation units (scene builder, C-ABI) are compiled by g++ and the kernels by hipcc, both
-with ``-ffp-contract=off``: the Mode R parity contract is bit-level and the reference (x86-64,
+with ``-ffp-contract=off`` and both refusing an external function without a declaration (the units' common
+interface is csrc/gi_launch.h): the Mode R parity contract is bit-level and the reference (x86-64,
 no FMA) never contracts a*b+c.  Run ``python -m 2019global_amd.build`` or ``__graft_entry__.build()``.
 """
 from __future__ import annotations
@@ -22,8 +23,8 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 ARCH = "gfx950"
 
 HOST_SRCS = ["gi_build.cpp", "gi_bvh.cpp", "gi_capi.cpp", "gi_multi.cpp", "gi_obj.cpp"]
-DEV_SRCS = ["gi_kernels.hip", "gi_wf.hip"]
-HEADERS = ["gi_math.h", "gi_scene.h", "gi_internal.h", "gi_dev.h", "gi_seg_ring.h"]
+DEV_SRCS = ["gi_kernels.hip", "gi_mode_r.hip", "gi_wf.hip"]
+HEADERS = ["gi_math.h", "gi_scene.h", "gi_internal.h", "gi_launch.h", "gi_dev.h", "gi_seg_ring.h"]
 
 COMMON = ["-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", f"-I{INCLUDE}", f"-I{CSRC}"]
 
@@ -72,8 +73,8 @@ def build(verbose: bool = False, force: bool = False, variant: str = "", hip_def
         src, obj = os.path.join(CSRC, s), os.path.join(objdir, s + ".o")
         defs = [f'-DGI_BUILD_ID="{bid}"'] if s == "gi_capi.cpp" else []
         if force or _stale(obj, [src] + hdrs) or (defs and old_bid != bid):
-            _run(["g++", "-O2", *COMMON, *defs, "-D__HIP_PLATFORM_AMD__", f"-I{ROCM}/include", "-c", src, "-o", obj],
-                 verbose)
+            _run(["g++", "-O2", "-Werror=missing-declarations", *COMMON, *defs, "-D__HIP_PLATFORM_AMD__", f"-I{ROCM}/include",
+                  "-c", src, "-o", obj], verbose)
         objs.append(obj)
     with open(bid_file, "w") as f:
         f.write(bid + "\n")
@@ -84,8 +85,8 @@ def build(verbose: bool = False, force: bool = False, variant: str = "", hip_def
         if force or _stale(obj, [src] + hdrs):
             # (A/B variants only: GI_VARIANT_FLAGS adds code-generation flags, e.g. -mllvm scheduler options)
             extra = os.environ.get("GI_VARIANT_FLAGS", "").split() if variant else []
-            cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-Wshadow", *COMMON, *[f"-D{d}" for d in hip_defines],
-                   *extra, "-munsafe-fp-atomics", "-c", src, "-o", obj]
+            cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-Wshadow", "-Werror=missing-prototypes", *COMMON,
+                   *[f"-D{d}" for d in hip_defines], *extra, "-munsafe-fp-atomics", "-c", src, "-o", obj]
             if verbose:
                 print(" ".join(cmd), flush=True)
             jobs.append((cmd, subprocess.Popen(cmd)))

@@ -1,6 +1,6 @@
 // gi_capi.cpp — the extern "C" boundary (include/gi.h).  Host-side only: validates arguments,
 // builds the scene (gi_build.cpp), owns its HBM copy, and launches the gfx950 kernels
-// (gi_kernels.hip).  There is no CPU rendering path: without a gfx950 device every render fails.
+// (gi_launch.h).  There is no CPU rendering path: without a gfx950 device every render fails.
 // No exception crosses the boundary: every entry point that can allocate runs inside guard(),
 // which maps std::bad_alloc to GI_ERR_NOMEM and anything else to GI_ERR_INTERNAL.
 #include <hip/hip_runtime_api.h>
@@ -16,36 +16,8 @@
 
 #include "gi.h"
 #include "gi_internal.h"
+#include "gi_launch.h"
 #include "gi_scene.h"
-
-namespace gi {
-bool build_host_scene(const gi_scene_desc& desc, HostScene& hs, std::string& err);
-long long shard_tiles(int w, int h, int shard_count);
-hipError_t x_launch_config(const DevScene& sc, int device, XLaunchCfg& cfg);
-int x_form_choice(const DevScene& sc, const XLaunchCfg& xc, const gi_opts& o);
-long long x_wf_chunk();
-int x_env_rf_per_slot();
-int r_kernel_choice(const DevScene& sc, const gi_opts& o);
-unsigned rf_own_pairs();
-unsigned rf_page_pairs();
-unsigned rf_max_pages();
-unsigned rf_seg_pairs();
-hipError_t launch_render(const DevScene& sc, const XLaunchCfg& xc, const CamDev& cam, V3 light, int w, int h, int y0,
-                         const gi_opts& o, double* rgb, uint8_t* rgb8, const XScratch& xs, KTimer* kt,
-                         hipStream_t stream);
-hipError_t launch_unshard(int w, int h, int shard_count, const double* packed, const uint8_t* packed8, double* rgb,
-                          uint8_t* rgb8, hipStream_t stream);
-hipError_t launch_trace_ray(const DevScene& sc, V3 o, V3 d, V3 light, int32_t* out_i, double* out_d, hipStream_t stream);
-hipError_t launch_box_kat(int n, const double* recs, int32_t* out, hipStream_t stream);
-hipError_t launch_x_query(const DevScene& sc, const XLaunchCfg& xc, V3 cam_pos, int flags, int n, const double* recs,
-                          int32_t* oi, double* od, hipStream_t stream);
-void x_query_variant(const DevScene& sc, const XLaunchCfg& xc, int flags, int32_t out[6]);
-hipError_t launch_x_texel_kat(const DevScene& sc, XVariant var, int n, int mode, const double* recs, int32_t* oi, double* od,
-                              hipStream_t stream);
-hipError_t launch_ray_query(const DevScene& sc, const XLaunchCfg& xc, bool any, const CastIO& io, hipStream_t stream);
-hipError_t launch_aov(const DevScene& sc, const XLaunchCfg& xc, const CamDev& cam, const AovIO& io, hipStream_t stream);
-hipError_t launch_cam_rays(const CamDev& cam, int x0, int y0, int cols, int rows, double* rays, hipStream_t stream);
-}  // namespace gi
 
 using namespace gi;
 
@@ -144,17 +116,17 @@ int ensure_xscratch(gi_scene* s, int w, int h, const gi_opts* o) {
     const long long need = shard_tiles(w, h, o->shard_count) * GI_TILE * GI_TILE;
     hipError_t e;
     if (o->mode == GI_MODE_R) {
-        // the flat Mode R phases' buffers, only when this launch runs them (r_kernel_choice == 1).
+        // the flat Mode R phases' buffers, only when this launch runs them (r_kernel_choice: RK_FLAT).
         // Pairs are one word: per tile its own GI_RF_S0 (8 per pixel slot), plus a shared pool of
         // GI_RF_PER_SLOT (16) per pixel slot in pages; with the per-slot directions and best ranks a
         // 1080p frame takes 0.28 GB (R-C4 writes 5.0 M pairs: 20 MB).  A tile whose candidates do not
         // fit is rendered by k_mode_r_batch; if the buffers cannot be had at all, the whole frame is.
         XScratch& x = s->xs;
-        if (r_kernel_choice(s->dev, *o) == 1 && x.rf_slots < need && !(x.rf_failed > 0 && need >= x.rf_failed)) {
+        if (r_kernel_choice(s->dev, *o) == RK_FLAT && x.rf_slots < need && !(x.rf_failed > 0 && need >= x.rf_failed)) {
             free_rflat(x);
             const hipError_t prior = hipPeekAtLastError();   // (a caller's unchecked error is left as it was)
             const long long tiles = need / 64;
-            const long long pages = (long long)x_env_rf_per_slot() * need / (long long)rf_page_pairs();
+            const long long pages = (long long)x_env().rf_per_slot * need / (long long)rf_page_pairs();
             const size_t pairs = (size_t)tiles * rf_own_pairs() + (size_t)pages * rf_page_pairs();
             // segments of k_rf_hit: a tile's pairs cut every rf_seg_pairs(), so at most one per tile
             // plus one per rf_seg_pairs() of the buffer
@@ -206,13 +178,13 @@ int ensure_xscratch(gi_scene* s, int w, int h, const gi_opts* o) {
             return hip_fail(e, "hipMalloc (per-sample radiance)");
         x.spp = o->spp;
     }
-    const int form = x_form_choice(s->dev, s->xcfg, *o);
-    if (form) {   // wavefront forms: counters; form 1 also path queues sized to a chunk of units
-        const long long want = std::max(64ll, std::min(x_wf_chunk(), need * (long long)o->spp));
+    const XForm form = x_form_choice(s->dev, s->xcfg, *o);
+    if (form != XFORM_MEGA) {   // gi_wf.hip's forms: counters; the wavefront form also path queues sized to a chunk of units
+        const long long want = std::max(64ll, std::min(kXWfChunk, need * (long long)o->spp));
         if (!x.wcnt) {
             if ((e = hipMalloc((void**)&x.wcnt, 2 * 64 * sizeof(unsigned))) != hipSuccess) return hip_fail(e, "hipMalloc (wavefront counters)");
         }
-        if (form == 1 && x.wcap < want) {
+        if (form == XFORM_WF && x.wcap < want) {
             for (int q = 0; q < 2; ++q) {
                 (void)hipFree(x.wq[q]);
                 (void)hipFree(x.wid[q]);
@@ -429,6 +401,7 @@ int check_opts(int w, int h, const gi_opts* o) {
 // Progressive passes (gi_opts sample_begin / sample_end) continue one frame on one scene: the first
 // pass (sample_begin 0) records the frame's key, a later one must match it and start where the
 // previous pass ended.  Any other render of the scene ends the frame.
+namespace {
 uint64_t prog_key(const gi_camera& c, const double light[3], int w, int h, const gi_opts& o) {
     uint64_t k = 1469598103934665603ull;
     auto mix = [&](const void* p, size_t n) {
@@ -467,6 +440,7 @@ int prog_check(gi_scene* s, const gi_camera& c, const double light[3], int w, in
 void prog_done(gi_scene* s, const gi_opts& o) {
     s->prog_next = (o.sample_end > 0 && o.sample_end < o.spp) ? o.sample_end : -1;
 }
+}  // namespace
 
 int band_rows_of(const gi_opts* o, int h) {
     int band = o->band_rows > 0 ? o->band_rows : h;
@@ -786,7 +760,7 @@ int gi_scene_seg_ring(gi_scene* s, const gi_opts* o, int32_t* on) {
     return guard([&]() -> int {
         if (!s || !o || !on) return fail(GI_ERR_ARG, "null argument");
         std::lock_guard<std::mutex> lk(s->mu);
-        *on = (x_form_choice(s->dev, s->xcfg, *o) == 2 && s->xcfg.seg_ring) ? 1 : 0;
+        *on = (x_form_choice(s->dev, s->xcfg, *o) == XFORM_SEG && s->xcfg.seg_ring) ? 1 : 0;
         return GI_OK;
     });
 }
@@ -796,7 +770,7 @@ int gi_scene_r_kernel(gi_scene* s, const gi_opts* o, int32_t* kernel) {
         if (!s || !o || !kernel) return fail(GI_ERR_ARG, "null argument");
         std::lock_guard<std::mutex> lk(s->mu);
         *kernel = r_kernel_choice(s->dev, *o);
-        if (*kernel == 1 && s->xs.rf_failed > 0 && s->xs.rf_slots == 0) *kernel = 2;   // (its buffers failed)
+        if (*kernel == RK_FLAT && s->xs.rf_failed > 0 && s->xs.rf_slots == 0) *kernel = RK_BATCH;   // (its buffers failed)
         return GI_OK;
     });
 }
@@ -855,7 +829,7 @@ int ray_query_device(gi_scene* s, bool any, const CastIO& io, hipStream_t stream
     if (reinterpret_cast<uintptr_t>(io.rays) & 15) return fail(GI_ERR_ARG, "device ray records must be 16-byte aligned");
     int rc = bind_device(s->device);
     if (rc) return rc;
-    const hipError_t e = launch_ray_query(s->dev, s->xcfg, any, io, stream);
+    const hipError_t e = launch_cast(s->dev, x_query_cfg(s->xcfg, 0, any ? WK_OCCL : WK_CAST), any, io, stream);
     return e == hipSuccess ? GI_OK : hip_fail(e, any ? "gi_occluded launch" : "gi_intersect launch");
 }
 // device staging of a host call: freed on scope exit
@@ -977,7 +951,7 @@ int gi_render_aov_device(gi_scene* s, const gi_camera* cam, const gi_aov_frame* 
         if (aov_all_null(*d_out)) return fail(GI_ERR_ARG, "gi_render_aov: every output is null");
         if (empty) return GI_OK;
         if ((rc = bind_device(s->device))) return rc;
-        const hipError_t e = launch_aov(s->dev, s->xcfg, make_cam(*cam, frame->w), aov_io(*frame, *d_out), static_cast<hipStream_t>(stream));
+        const hipError_t e = launch_aov(s->dev, x_query_cfg(s->xcfg, 0, WK_AOV), make_cam(*cam, frame->w), aov_io(*frame, *d_out), static_cast<hipStream_t>(stream));
         return e == hipSuccess ? GI_OK : hip_fail(e, "gi_render_aov launch");
     });
 }
@@ -1005,7 +979,7 @@ int gi_render_aov(gi_scene* s, const gi_camera* cam, const gi_aov_frame* frame, 
         if (e != hipSuccess) return hip_fail(e, "hipMalloc (feature buffer staging)");
         const gi_aov d{static_cast<double*>(dt.p), static_cast<double*>(dn.p), static_cast<double*>(da.p),
                        static_cast<int32_t*>(dp.p), static_cast<int32_t*>(de.p), static_cast<int32_t*>(du.p)};
-        e = launch_aov(s->dev, s->xcfg, make_cam(*cam, frame->w), aov_io(*frame, d), nullptr);
+        e = launch_aov(s->dev, x_query_cfg(s->xcfg, 0, WK_AOV), make_cam(*cam, frame->w), aov_io(*frame, d), nullptr);
         if (e != hipSuccess) return hip_fail(e, "gi_render_aov launch");
         if (out->t) e = hipMemcpy(out->t, dt.p, m * sizeof(double), hipMemcpyDeviceToHost);   // (synchronous copies on the launch's stream)
         if (e == hipSuccess && out->normal) e = hipMemcpy(out->normal, dn.p, m * 3 * sizeof(double), hipMemcpyDeviceToHost);
@@ -1089,7 +1063,7 @@ int gi_kat_x_query(gi_scene* s, int n, const double* recs, const double cam_pos[
             e = hipMalloc((void**)&d_d, hd.size() * sizeof(double));
         if (e == hipSuccess) e = hipMemcpy(d_r, recs, (size_t)n * 12 * sizeof(double), hipMemcpyHostToDevice);
         if (e == hipSuccess)
-            e = launch_x_query(s->dev, s->xcfg, v3(cam_pos[0], cam_pos[1], cam_pos[2]), flags, n, d_r, d_i, d_d, nullptr);
+            e = launch_x_query_kat(s->dev, x_query_cfg(s->xcfg, flags, WK_SEG), v3(cam_pos[0], cam_pos[1], cam_pos[2]), n, d_r, d_i, d_d, nullptr);
         if (e == hipSuccess) e = hipMemcpy(hi.data(), d_i, hi.size() * sizeof(int32_t), hipMemcpyDeviceToHost);
         if (e == hipSuccess) e = hipMemcpy(hd.data(), d_d, hd.size() * sizeof(double), hipMemcpyDeviceToHost);
         (void)hipFree(d_r);
@@ -1114,7 +1088,7 @@ int gi_kat_x_variant(gi_scene* s, int flags, int32_t out[6]) {
     return guard([&]() -> int {
         if (!s || !out || (flags & ~3) != 0) return fail(GI_ERR_ARG, "bad arguments");
         std::lock_guard<std::mutex> lk(s->mu);
-        x_query_variant(s->dev, s->xcfg, flags, out);
+        wf_variant(s->dev, x_query_cfg(s->xcfg, flags, WK_SEG), out);   // with flags 0, k_seg's for this scene
         return GI_OK;
     });
 }

@@ -1,6 +1,7 @@
-// gi_dev.h — device code shared by the gfx950 kernel translation units (gi_kernels.hip: Mode R and
-// the persistent Mode X kernel; gi_wf.hip: the wavefront Mode X kernels): camera, tile map, the
-// Mode X wide-node / leaf-record tests and texture mapping.  Header-only (internal linkage per TU).
+// gi_dev.h — device code shared by the gfx950 kernel translation units (gi_mode_r.hip: Mode R;
+// gi_kernels.hip: the persistent Mode X kernel with its classify and reduce passes; gi_wf.hip: k_wf_bounce,
+// k_seg, k_cast, k_aov): camera rays, tile map, the Mode X wide-node / leaf-record tests and texture
+// mapping.  Header-only (internal linkage per TU).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,11 +13,6 @@
 #include "gi_scene.h"
 
 namespace gi {
-struct CamDev {
-    V3 pos, up, left, top_left;
-    double rx, ry;
-};
-
 namespace {
 
 constexpr int kTile = GI_TILE;

@@ -1,5 +1,5 @@
-// gi_internal.h — declarations shared by the host translation units of libgi (gi_capi.cpp,
-// gi_multi.cpp).  Not part of the C-ABI.
+// gi_internal.h — what gi_capi.cpp defines for the other host translation units of libgi (gi_multi.cpp,
+// gi_obj.cpp).  Not part of the C-ABI.  The kernel units' host functions are declared in gi_launch.h.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -13,12 +13,6 @@
 #include "gi_scene.h"
 
 namespace gi {
-
-// camera basis and frame corner of raytracer.h:26-30 (the kernels' CamDev, gi_kernels.hip)
-struct CamDev {
-    V3 pos, up, left, top_left;
-    double rx, ry;
-};
 
 int error(int code, const std::string& msg) noexcept;      // sets gi_last_error, returns code
 int hip_error(hipError_t e, const char* what) noexcept;    // GI_ERR_DEVICE with HIP's message

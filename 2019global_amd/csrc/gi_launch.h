@@ -1,0 +1,86 @@
+// gi_launch.h — the host functions that libgi's kernel units (gi_kernels.hip, gi_mode_r.hip, gi_wf.hip)
+// define for each other and for gi_capi.cpp.  The only place where a cross-unit function is declared: the
+// unit that defines one and the units that call it all include this header.  Host-only, no device code.
+#pragma once
+
+#include <hip/hip_runtime_api.h>
+
+#include "gi.h"
+#include "gi_scene.h"
+
+namespace gi {
+
+// Read once per process from the environment (thread-safe; several host threads may each drive their
+// own device and scene).  One user knob: GI_X_MAX_RUN, the largest Mode X work-unit run length (scenes
+// of cheap background samples such as the main.cpp scene prefer 8).  The rest are TEST hooks that pick
+// among kernels whose frames are identical bit for bit (tests/test_gpu_parity.py compares them):
+// GI_X_WF (0/1/2: force a Mode X form for a whole suite run), GI_X_HELP=0 (no shadow-ray handoff),
+// GI_X_FLAT=0 (k_seg / k_wf_bounce walk the tree even where the scene's flat leaf table applies),
+// GI_SEG_RING=0 (k_seg's lanes make their own units even where the per-wave ring fits),
+// GI_R_FLAT (0/1/2: force a Mode R kernel), GI_RF_PER_SLOT (the flat Mode R pool size: 0 forces the
+// per-tile overflow path), GI_RF_GROUP (1/4: force k_rf_reach's lanes per hit).
+struct XEnv {
+    int run_log2 = 0, help = 1, wf = -1, flat = 1, seg_ring = 1;
+    int r_flat = -1;                  // Mode R kernels (GI_R_FLAT): 1 the flat phases for every scene, 0 k_mode_r
+                                      // for every scene, 2 k_mode_r_batch for the whole frame (tests); -1 by size
+    int rf_per_slot = 16;             // flat Mode R: pool pairs per pixel slot of the frame (GI_RF_PER_SLOT)
+    int rf_group = 0;                 // k_rf_reach lanes per hit (GI_RF_GROUP): 0 by the launch's hits, 1 or 4 (tests)
+};
+const XEnv& x_env();
+
+// One launch of a gi_wf.hip kernel: the instantiation (var, flat: wf_dispatch), its dynamic LDS and the
+// kernel's resident workgroups (XLaunchCfg::wf_grid; unused where the grid follows the input alone).
+struct XKernelCfg {
+    XVariant var;
+    bool flat;
+    size_t lds_bytes;
+    int resident;
+};
+
+// ---- gi_kernels.hip: k_mode_x with its classify and reduce passes, k_unshard ----
+long long shard_tiles(int w, int h, int shard_count);
+constexpr long long kXWfChunk = 8ll << 20;   // wavefront form: units (pixel samples) per chunk = queue capacity
+hipError_t x_launch_config(const DevScene& sc, int device, XLaunchCfg& cfg);
+XForm x_form_choice(const DevScene& sc, const XLaunchCfg& xc, const gi_opts& o);
+hipError_t launch_render(const DevScene& sc, const XLaunchCfg& xc, const CamDev& cam, V3 light, int w, int h, int y0,
+                         const gi_opts& o, double* rgb, uint8_t* rgb8, const XScratch& xs, KTimer* kt,
+                         hipStream_t stream);
+hipError_t launch_unshard(int w, int h, int shard_count, const double* packed, const uint8_t* packed8, double* rgb,
+                          uint8_t* rgb8, hipStream_t stream);
+
+// ---- gi_mode_r.hip: the Mode R kernels, k_trace_ray, k_box_kat ----
+RKernel r_kernel_choice(const DevScene& sc, const gi_opts& o);
+// the GI_RF_* values gi_mode_r.hip was compiled with: the build hands its -D flags to the kernel units only
+unsigned rf_own_pairs();
+unsigned rf_page_pairs();
+unsigned rf_max_pages();
+unsigned rf_seg_pairs();
+// launch_render's Mode R half: the frame's kernels, between ev_begin and ev_end where they are not null
+hipError_t launch_mode_r(const DevScene& sc, const CamDev& cam, V3 light, int w, int h, int y0, const gi_opts& o,
+                         double* rgb, uint8_t* rgb8, const XScratch& xs, hipStream_t stream, hipEvent_t ev_begin,
+                         hipEvent_t ev_end);
+hipError_t launch_trace_ray(const DevScene& sc, V3 o, V3 d, V3 light, int32_t* out_i, double* out_d, hipStream_t stream);
+hipError_t launch_box_kat(int n, const double* recs, int32_t* out, hipStream_t stream);
+
+// ---- gi_wf.hip: k_wf_bounce, k_seg, k_cast, k_aov, k_cam_rays, the query and texel KATs ----
+size_t wf_lds_bytes(const DevScene& sc, bool lds, bool flat);   // of k_wf_bounce and its kin, without the ring
+size_t wf_seg_ring_bytes();
+hipError_t wf_occupancy(const DevScene& sc, WfKernel k, const XKernelCfg& c, int* per_cu);
+// A query launch (k_cast, k_aov, the KAT) on a scene: the variant, the flat choice and the dynamic LDS of a
+// k_seg launch (launch_render's), with kernel k's resident workgroups.  flags (the KAT's; 0 elsewhere) bit 0:
+// the tree walk where the flat table would apply (GI_X_FLAT=0 in process); bit 1: the HBM-resident variants
+// (the level stack instead of the staged scene) for a scene that would be staged in LDS.
+XKernelCfg x_query_cfg(const XLaunchCfg& xc, int flags, WfKernel k);
+hipError_t launch_wf(const DevScene& sc, const XKernelCfg& c, XForm form, const CamDev& cam, V3 light, int w, int h, int y0,
+                     const gi_opts& o, double* rgb, uint8_t* rgb8, const XScratch& xs, const unsigned* n_list_dev,
+                     unsigned long long* stats, int xflags, hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end);
+hipError_t launch_x_query_kat(const DevScene& sc, const XKernelCfg& c, V3 cam_pos, int n, const double* recs, int32_t* oi,
+                              double* od, hipStream_t stream);
+hipError_t launch_x_texel_kat(const DevScene& sc, XVariant var, int n, int mode, const double* recs, int32_t* oi, double* od,
+                              hipStream_t stream);
+hipError_t launch_cast(const DevScene& sc, const XKernelCfg& c, bool any, const CastIO& io, hipStream_t stream);
+hipError_t launch_aov(const DevScene& sc, const XKernelCfg& c, const CamDev& cam, const AovIO& io, hipStream_t stream);
+hipError_t launch_cam_rays(const CamDev& cam, int x0, int y0, int cols, int rows, double* rays, hipStream_t stream);
+void wf_variant(const DevScene& sc, const XKernelCfg& c, int32_t out[6]);
+
+}  // namespace gi

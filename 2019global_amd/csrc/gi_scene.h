@@ -9,12 +9,21 @@
 // XPrim[] shading records).
 #pragma once
 #include <stdint.h>
+#include <string>
 #include <type_traits>
 #include <vector>
 
+#include "gi.h"
 #include "gi_math.h"
 
 namespace gi {
+
+// camera basis and frame corner of raytracer.h:26-30: made on the host (gi_capi.cpp make_cam), passed to
+// the kernels by value
+struct CamDev {
+    V3 pos, up, left, top_left;
+    double rx, ry;
+};
 
 enum EntKind : int32_t { K_IMP_SPHERE = 1, K_IMP_TRIANGLE = 2, K_EXP_QUAD = 3, K_EXP_SPHERE = 4, K_EXP_CUBE = 5,
                          K_EXP_CONE = 6, K_EXP_RECTANGLE = 7, K_EXP_BOX = 8 };
@@ -187,6 +196,8 @@ struct HostScene {
     bool x_flat_ok = false;          // xflat fits the flat query: <= GI_XFLAT_MAX leaves of <= 255 records each,
                                      // offsets below 2^16 (wf_flat packs offset, index and count in a word)
 };
+// Builds every host structure of a scene from its description (gi_build.cpp); false: err says why.
+bool build_host_scene(const gi_scene_desc& desc, HostScene& hs, std::string& err);
 // Fills hs.xflat / x_flat_ok from hs.xwnodes (after assign_plane_groups: the group bytes are copied).
 void build_xflat(HostScene& hs);
 
@@ -277,7 +288,7 @@ struct XScratch {
     unsigned* wid[2] = {nullptr, nullptr};
     unsigned* wcnt = nullptr;
     long long wcap = 0;
-    // flat Mode R (gi_kernels.hip k_rf_*): candidate pairs, one word each -- every tile's own region
+    // flat Mode R (gi_mode_r.hip k_rf_*): candidate pairs, one word each -- every tile's own region
     // of GI_RF_S0, then the pool of rf_pages pages of GI_RF_PAGE (rf_pairs holds both); per tile its
     // pool page ids (GI_RF_KMAX), its pairs / hits and its first chunk of hits; per pixel slot the best
     // rank + 1 and the primary direction; the counters (pool pages taken, overflowed tiles) and the
@@ -335,6 +346,17 @@ void with_bools(F&& f, bool b, R... r) {
     else with_bools<Bs..., false>(f, r...);
 }
 
+// Mode X form of a launch (x_form_choice; the values are gi_scene_x_form's, part of the ABI): the
+// persistent path-state kernel (k_mode_x), the wavefront form (k_wf_bounce once per bounce over compacted
+// queues), the segment-synchronous form (k_seg).
+enum XForm : int { XFORM_MEGA = 0, XFORM_WF = 1, XFORM_SEG = 2 };
+// Mode R kernel of a launch (r_kernel_choice; the values are gi_scene_r_kernel's, part of the ABI): k_mode_r
+// (one lane per pixel), the flat phases (k_rf_*), k_mode_r_batch for the whole frame.
+enum RKernel : int { RK_PIXEL = 0, RK_FLAT = 1, RK_BATCH = 2 };
+// gi_wf.hip's kernels whose occupancy is queried per scene (wf_occupancy): k_wf_bounce, k_seg, k_seg with
+// its per-wave ring, k_cast closest hit and any hit, k_aov.
+enum WfKernel { WK_BOUNCE, WK_SEG, WK_SEG_RING, WK_CAST, WK_OCCL, WK_AOV, WK_COUNT };
+
 // Mode X launch configuration, computed once per scene when it is created (gi_capi.cpp, on the
 // scene's device): kernel variant, dynamic LDS bytes and the resident persistent grids.
 struct XLaunchCfg {
@@ -343,13 +365,9 @@ struct XLaunchCfg {
     int resident = 1;        //   and its resident 256-thread workgroups on the device (occupancy x CUs)
     size_t wf_lds_bytes = 0; // gi_wf.hip's kernels (k_wf_bounce, k_cast, k_aov, the query KAT): dynamic LDS per workgroup
     size_t wf_tree_lds_bytes = 0;   //   the same for the tree walk where the flat query is the default (the KAT's flag)
-    int wf_resident = 1;     //   and the resident workgroups of k_wf_bounce
-    int seg_resident = 1;    //   and of k_seg
+    int wf_grid[WK_COUNT] = {};     //   and each kernel's resident workgroups (WK_SEG_RING: with the ring's LDS)
     bool seg_ring = false;   // k_seg refills from its per-wave ring: its LDS does not lower k_seg's resident workgroups
     size_t seg_lds_bytes = 0;//   k_seg's dynamic LDS: wf_lds_bytes, and the ring's bytes with seg_ring
-    int cast_resident = 1;   // the ray queries (k_cast, gi_wf.hip): closest hit
-    int occl_resident = 1;   //   and any hit
-    int aov_resident = 1;    // the feature buffers (k_aov, gi_wf.hip)
 };
 
 // One call of the public ray queries (gi_intersect*, gi_occluded*; gi_wf.hip k_cast): device pointers.

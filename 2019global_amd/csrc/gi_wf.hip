@@ -25,6 +25,7 @@
 
 #include "gi.h"
 #include "gi_dev.h"
+#include "gi_launch.h"
 #include "gi_scene.h"
 #include "gi_seg_ring.h"
 
@@ -412,7 +413,7 @@ __device__ __forceinline__ WFView wf_stage(const DevScene& sc, int4* lds) {
     v.EN = sc.ents;
     v.FT = sc.xflat;
     if constexpr (LDS) {
-        // (FLAT: no kernel's flat query reads the wide nodes -- not staged, not counted by wf_scene_lds_bytes)
+        // (FLAT: no kernel's flat query reads the wide nodes -- not staged, not counted by wf_lds_bytes)
         const int nw = FLAT ? 0 : sc.n_xwnodes * (int)(sizeof(XWNode) / sizeof(int4));
         const int nh = sc.n_xhot * (int)(sizeof(XHot) / sizeof(int4));
         const int np = sc.n_xprims * (int)(sizeof(XPrim) / sizeof(int4));
@@ -425,7 +426,7 @@ __device__ __forceinline__ WFView wf_stage(const DevScene& sc, int4* lds) {
         for (int i = threadIdx.x; i < nh; i += blockDim.x) lds[nw + i] = gh[i];
         for (int i = threadIdx.x; i < np; i += blockDim.x) lds[nw + nh + i] = gp[i];
         for (int i = threadIdx.x; i < ne; i += blockDim.x) lds[nw + nh + np + i] = ge[i];
-        // FLAT: the leaves' candidate words behind the entities (kFlatPkBytes, counted by wf_scene_lds_bytes)
+        // FLAT: the leaves' candidate words behind the entities (kFlatPkBytes, counted by wf_lds_bytes)
         constexpr int nk = FLAT ? (int)(kFlatPkBytes / sizeof(int4)) : 0;
         if constexpr (FLAT) {
             uint32_t* pkw = reinterpret_cast<uint32_t*>(lds + nw + nh + np + ne);
@@ -1263,26 +1264,27 @@ __global__ __launch_bounds__(256) void k_cam_rays(CamDev cam, int x0, int y0, in
 
 }  // namespace
 
-// dynamic LDS of the bounce kernel beyond the scene / level stack: the per-lane path slots
-size_t wf_slot_bytes() { return kWfSlotBytes; }
-// the scene's share of that LDS (LDS-resident scenes): the staged records (entity records included:
-// read from global memory by the shading instead, C3 4.65 -> 4.69 ms, and 5 waves per SIMD with them
-// there, 96 VGPRs and 120 B of scratch, 4.79 ms; profiles/r06_ab.txt)
-// (and, where the flat leaf table applies, its per-leaf candidate words).  flat: the launch runs the flat
-// kernels, which do not stage the wide nodes (wf_stage)
-size_t wf_scene_lds_bytes(const DevScene& sc, bool flat) {
+// dynamic LDS of the bounce kernel and its kin: the per-lane path slots behind the level stack (lds false:
+// the HBM-resident variants) or behind the staged scene's records (entity records included: read from
+// global memory by the shading instead, C3 4.65 -> 4.69 ms, and 5 waves per SIMD with them there, 96 VGPRs
+// and 120 B of scratch, 4.79 ms; profiles/r06_ab.txt) and, where the flat leaf table applies, its per-leaf
+// candidate words.  flat: the launch runs the flat kernels, which do not stage the wide nodes (wf_stage)
+constexpr size_t kWfStackBytes = 16 * 256 * sizeof(int);
+size_t wf_lds_bytes(const DevScene& sc, bool lds, bool flat) {
     const size_t nodes = (flat && sc.x_flat) ? (size_t)sc.n_xwnodes * sizeof(XWNode) : 0;
-    return (size_t)sc.x_lds_bytes - nodes + (sc.x_flat ? kFlatPkBytes : 0);
+    return (lds ? (size_t)sc.x_lds_bytes - nodes + (sc.x_flat ? kFlatPkBytes : 0) : kWfStackBytes) + kWfSlotBytes;
 }
 // dynamic LDS of a k_seg launch that runs the ring (XF_SEG_RING), beyond the other kernels' bytes
 size_t wf_seg_ring_bytes() { return kSegRingBytes; }
 
-// The kernel variant for a scene: f(XTag) (var: XLaunchCfg::var; flat: the flat leaf query, LDS-resident
+// The kernel variant for a scene: f(XTag) (c.var: XLaunchCfg::var; c.flat: the flat leaf query, LDS-resident
 // scenes whose table applies -- DevScene::x_flat -- unless GI_X_FLAT=0).  TRI of an LDS-resident scene is
 // its W4 (light shading); HBM-resident scenes run SH = false.
+namespace {
 template <typename F>
-void wf_dispatch(const DevScene& sc, XVariant var, bool flat, bool stats, F&& f) {
-    if (var.lds && flat && sc.x_flat)   // (SH only shapes the tree walk's level masks: one flat kernel per W4)
+void wf_dispatch(const DevScene& sc, const XKernelCfg& c, bool stats, F&& f) {
+    const XVariant var = c.var;
+    if (var.lds && c.flat && sc.x_flat)   // (SH only shapes the tree walk's level masks: one flat kernel per W4)
         with_bools([&](auto S, auto W) { f(XTag<S.value, true, W.value, true, W.value, false, true>{}); }, stats, var.w4);
     else if (var.lds)
         with_bools([&](auto S, auto W, auto H) { f(XTag<S.value, true, W.value, H.value, W.value, false, false>{}); },
@@ -1301,52 +1303,62 @@ constexpr auto cast_kernel(V) { return &k_cast<ANY, V::lds, V::w4, V::sh, V::tri
 
 template <typename V>
 constexpr auto aov_kernel(V) { return &k_aov<V::lds, V::w4, V::sh, V::tri, V::cn, V::flat>; }
+}  // namespace
 
-// resident workgroups per CU of the kernel a form (1: k_wf_bounce, 2: k_seg, 6: k_seg with the ring; the ray queries: 3 k_cast
-// closest hit, 4 k_cast any hit; 5: the feature buffers, k_aov) runs for this scene
-hipError_t wf_occupancy(const DevScene& sc, XVariant var, bool flat, size_t lds_bytes, int form, int* per_cu) {
+XKernelCfg x_query_cfg(const XLaunchCfg& xc, int flags, WfKernel k) {
+    const bool hbm = (flags & 2) != 0 && xc.var.lds;
+    const bool flat = x_env().flat && (flags & 1) == 0;
+    return XKernelCfg{hbm ? XVariant{} : xc.var, flat,
+                      hbm ? kWfStackBytes + kWfSlotBytes : flat ? xc.wf_lds_bytes : xc.wf_tree_lds_bytes, xc.wf_grid[k]};
+}
+
+// resident workgroups per CU of kernel k in this scene's variant, with c.lds_bytes of dynamic LDS
+hipError_t wf_occupancy(const DevScene& sc, WfKernel k, const XKernelCfg& c, int* per_cu) {
     hipError_t e = hipSuccess;
-    wf_dispatch(sc, var, flat, false, [&](auto V) {
-        const void* f = form == 5   ? reinterpret_cast<const void*>(aov_kernel(V))
-                        : form == 4 ? reinterpret_cast<const void*>(cast_kernel<true>(V))
-                        : form == 3 ? reinterpret_cast<const void*>(cast_kernel<false>(V))
-                        : form == 6 ? reinterpret_cast<const void*>(seg_kernel<true>(V))
-                        : form == 2 ? reinterpret_cast<const void*>(seg_kernel<false>(V))
-                                    : reinterpret_cast<const void*>(bounce_kernel(V));
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, f, 256, lds_bytes);
+    wf_dispatch(sc, c, false, [&](auto V) {
+        const void* f = nullptr;
+        switch (k) {
+            case WK_BOUNCE: f = reinterpret_cast<const void*>(bounce_kernel(V)); break;
+            case WK_SEG: f = reinterpret_cast<const void*>(seg_kernel<false>(V)); break;
+            case WK_SEG_RING: f = reinterpret_cast<const void*>(seg_kernel<true>(V)); break;
+            case WK_CAST: f = reinterpret_cast<const void*>(cast_kernel<false>(V)); break;
+            case WK_OCCL: f = reinterpret_cast<const void*>(cast_kernel<true>(V)); break;
+            case WK_AOV: f = reinterpret_cast<const void*>(aov_kernel(V)); break;
+            case WK_COUNT: break;
+        }
+        e = f ? hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, f, 256, c.lds_bytes) : hipErrorInvalidValue;
     });
     return e;
 }
 
 // The Mode X pass after k_x_classify and before k_x_reduce in the wavefront forms.
-//  form 1 (wavefront): per chunk of units (the queue capacity; chunks for the launch's every pixel
+//  XFORM_WF (wavefront): per chunk of units (the queue capacity; chunks for the launch's every pixel
 //    slot, those past the work list's end return at once on the device) `depth` bounce launches;
 //    counters: 2 per bounce (take, n_out), zeroed per chunk.
-//  form 2 (segment-synchronous): one persistent launch; counter: a 64-bit unit count at xs.wcnt.
-hipError_t launch_wf(const DevScene& sc, XVariant var, size_t lds_bytes, int resident, int form, const CamDev& cam, V3 light,
-                     int w, int h, int y0, const gi_opts& o, double* rgb, uint8_t* rgb8, const XScratch& xs,
-                     const unsigned* n_list_dev, unsigned long long* stats, int xflags, hipStream_t stream,
-                     hipEvent_t ev_begin, hipEvent_t ev_end) {
+//  XFORM_SEG (segment-synchronous): one persistent launch; counter: a 64-bit unit count at xs.wcnt.
+// c.flat is the launch's choice (xflags without XF_NO_FLAT).
+hipError_t launch_wf(const DevScene& sc, const XKernelCfg& c, XForm form, const CamDev& cam, V3 light, int w, int h, int y0,
+                     const gi_opts& o, double* rgb, uint8_t* rgb8, const XScratch& xs, const unsigned* n_list_dev,
+                     unsigned long long* stats, int xflags, hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end) {
     const TileMap m = make_map(w, h, o.shard_count, o.shard_index, y0);
     const int depth = o.depth;
     const int s0 = o.sample_end > 0 ? o.sample_begin : 0, s1 = o.sample_end > 0 ? o.sample_end : o.spp;
-    const dim3 grid((unsigned)std::max(1, resident)), block(256);
+    const dim3 grid((unsigned)std::max(1, c.resident)), block(256);
     hipError_t e = hipSuccess;
-    const bool flat = (xflags & XF_NO_FLAT) == 0;   // (GI_X_FLAT=0)
-    if (form == 2) {   // (the unit counter xs.wcnt[0..1] was zeroed by k_x_classify)
-        WFArgs a{};
-        a.list = xs.list;
-        a.n_list = n_list_dev;
-        a.part = xs.part;
+    WFArgs a{};   // (the fields of a bounce stay zero in k_seg's)
+    a.list = xs.list;
+    a.n_list = n_list_dev;
+    a.part = xs.part;
+    a.s0 = (unsigned)s0;
+    a.ns = (unsigned)(s1 - s0);
+    if (form == XFORM_SEG) {   // (the unit counter xs.wcnt[0..1] was zeroed by k_x_classify)
         a.take = xs.wcnt;
-        a.s0 = (unsigned)s0;
-        a.ns = (unsigned)(s1 - s0);
         if (ev_begin) (void)hipEventRecord(ev_begin, stream);
-        wf_dispatch(sc, var, flat, stats != nullptr, [&](auto V) {
-            if (xflags & XF_SEG_RING)   // (lds_bytes then holds the ring's: XLaunchCfg::seg_lds_bytes)
-                hipLaunchKernelGGL(seg_kernel<true>(V), grid, block, lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, rgb, rgb8, stats, a, xflags);
+        wf_dispatch(sc, c, stats != nullptr, [&](auto V) {
+            if (xflags & XF_SEG_RING)   // (c.lds_bytes then holds the ring's: XLaunchCfg::seg_lds_bytes)
+                hipLaunchKernelGGL(seg_kernel<true>(V), grid, block, c.lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, rgb, rgb8, stats, a, xflags);
             else
-                hipLaunchKernelGGL(seg_kernel<false>(V), grid, block, lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, rgb, rgb8, stats, a, xflags);
+                hipLaunchKernelGGL(seg_kernel<false>(V), grid, block, c.lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, rgb, rgb8, stats, a, xflags);
         });
         if (ev_end) (void)hipEventRecord(ev_end, stream);
         return hipGetLastError();
@@ -1361,25 +1373,19 @@ hipError_t launch_wf(const DevScene& sc, XVariant var, size_t lds_bytes, int res
         e = hipMemsetAsync(xs.wcnt, 0, 2 * (size_t)depth * sizeof(unsigned), stream);
         if (e != hipSuccess) return e;
         for (int b = 0; b < depth; ++b) {
-            WFArgs a;
-            a.list = xs.list;
-            a.n_list = n_list_dev;
-            a.part = xs.part;
             a.take = xs.wcnt + 2 * b;
             a.n_in = b > 0 ? xs.wcnt + 2 * (b - 1) + 1 : nullptr;
             a.n_out = xs.wcnt + 2 * b + 1;
             a.u0 = u0;
             a.u1 = std::min(units, u0 + (unsigned long long)xs.wcap);
-            a.s0 = (unsigned)s0;
-            a.ns = (unsigned)(s1 - s0);
             WFQ qin, qout;
             qin.cap = qout.cap = xs.wcap;
             qin.r = xs.wq[(b + 1) & 1];
             qin.id = reinterpret_cast<uint2*>(xs.wid[(b + 1) & 1]);
             qout.r = xs.wq[b & 1];
             qout.id = reinterpret_cast<uint2*>(xs.wid[b & 1]);
-            wf_dispatch(sc, var, flat, stats != nullptr, [&](auto V) {
-                hipLaunchKernelGGL(bounce_kernel(V), grid, block, lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, b, rgb, rgb8, stats, a, qin, qout, xflags);
+            wf_dispatch(sc, c, stats != nullptr, [&](auto V) {
+                hipLaunchKernelGGL(bounce_kernel(V), grid, block, c.lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, b, rgb, rgb8, stats, a, qin, qout, xflags);
             });
         }
     }
@@ -1388,13 +1394,13 @@ hipError_t launch_wf(const DevScene& sc, XVariant var, size_t lds_bytes, int res
 }
 
 // gi_kat_x_query's launch: k_seg's variant for the scene (wf_dispatch), one ray per lane
-hipError_t launch_x_query_kat(const DevScene& sc, XVariant var, bool flat, size_t lds_bytes, V3 cam_pos, int n,
-                              const double* recs, int32_t* oi, double* od, hipStream_t stream) {
+hipError_t launch_x_query_kat(const DevScene& sc, const XKernelCfg& c, V3 cam_pos, int n, const double* recs, int32_t* oi,
+                              double* od, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
     const dim3 grid((unsigned)(((long long)n + 255) / 256)), block(256);
-    wf_dispatch(sc, var, flat, false, [&](auto V) {
+    wf_dispatch(sc, c, false, [&](auto V) {
         using T = decltype(V);
-        hipLaunchKernelGGL((k_x_query_kat<T::lds, T::w4, T::sh, T::tri, T::cn, T::flat>), grid, block, lds_bytes, stream, sc, cam_pos, n, recs, oi, od);
+        hipLaunchKernelGGL((k_x_query_kat<T::lds, T::w4, T::sh, T::tri, T::cn, T::flat>), grid, block, c.lds_bytes, stream, sc, cam_pos, n, recs, oi, od);
     });
     return hipGetLastError();
 }
@@ -1404,7 +1410,7 @@ hipError_t launch_x_texel_kat(const DevScene& sc, XVariant var, int n, int mode,
                               hipStream_t stream) {
     if (n <= 0) return hipSuccess;
     const dim3 grid((unsigned)(((long long)n + 255) / 256)), block(256);
-    wf_dispatch(sc, var, false, false, [&](auto V) {
+    wf_dispatch(sc, XKernelCfg{var, false, 0, 0}, false, [&](auto V) {
         using T = decltype(V);
         hipLaunchKernelGGL((k_x_texel_kat<T::tri>), grid, block, 0, stream, sc, n, mode, recs, oi, od);
     });
@@ -1412,30 +1418,28 @@ hipError_t launch_x_texel_kat(const DevScene& sc, XVariant var, int n, int mode,
 }
 
 // The ray queries' launch: k_seg's variant for the scene (wf_dispatch) over a persistent grid of at most
-// `resident` workgroups (wf_occupancy forms 3 / 4), fewer when the rays need fewer.  Asynchronous on
+// c.resident workgroups (wf_occupancy WK_CAST / WK_OCCL), fewer when the rays need fewer.  Asynchronous on
 // `stream`; no allocation, no copy, no synchronisation.
-hipError_t launch_cast(const DevScene& sc, XVariant var, bool flat, size_t lds_bytes, int resident, bool any, const CastIO& io,
-                       hipStream_t stream) {
+hipError_t launch_cast(const DevScene& sc, const XKernelCfg& c, bool any, const CastIO& io, hipStream_t stream) {
     if (io.n <= 0) return hipSuccess;
     const long long want = (io.n + 255) / 256;
-    const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>(want, resident))), block(256);
-    wf_dispatch(sc, var, flat, false, [&](auto V) {
-        if (any) hipLaunchKernelGGL(cast_kernel<true>(V), grid, block, lds_bytes, stream, sc, io);
-        else hipLaunchKernelGGL(cast_kernel<false>(V), grid, block, lds_bytes, stream, sc, io);
+    const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>(want, c.resident))), block(256);
+    wf_dispatch(sc, c, false, [&](auto V) {
+        if (any) hipLaunchKernelGGL(cast_kernel<true>(V), grid, block, c.lds_bytes, stream, sc, io);
+        else hipLaunchKernelGGL(cast_kernel<false>(V), grid, block, c.lds_bytes, stream, sc, io);
     });
     return hipGetLastError();
 }
 
 // The feature buffers' launch: k_aov in k_seg's variant for the scene (wf_dispatch) over a persistent grid
-// of at most `resident` workgroups (wf_occupancy form 5), fewer when the window needs fewer.
+// of at most c.resident workgroups (wf_occupancy WK_AOV), fewer when the window needs fewer.
 // Asynchronous on `stream`; no allocation, no copy, no synchronisation.
-hipError_t launch_aov_kernel(const DevScene& sc, XVariant var, bool flat, size_t lds_bytes, int resident, const CamDev& cam,
-                             const AovIO& io, hipStream_t stream) {
+hipError_t launch_aov(const DevScene& sc, const XKernelCfg& c, const CamDev& cam, const AovIO& io, hipStream_t stream) {
     if (io.cols <= 0 || io.rows <= 0) return hipSuccess;
     const long long want = (aov_batches(io.cols, io.rows) + 3) / 4;   // four waves (batches) per workgroup
-    const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>(want, resident))), block(256);
-    wf_dispatch(sc, var, flat, false, [&](auto V) {
-        hipLaunchKernelGGL(aov_kernel(V), grid, block, lds_bytes, stream, sc, cam, io);
+    const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>(want, c.resident))), block(256);
+    wf_dispatch(sc, c, false, [&](auto V) {
+        hipLaunchKernelGGL(aov_kernel(V), grid, block, c.lds_bytes, stream, sc, cam, io);
     });
     return hipGetLastError();
 }
@@ -1451,8 +1455,8 @@ hipError_t launch_cam_rays(const CamDev& cam, int x0, int y0, int cols, int rows
 }
 
 // the variant (LDS, W4, SH, TRI, CN, FLAT) wf_dispatch picks for a scene: what gi_kat_x_variant reports
-void wf_variant(const DevScene& sc, XVariant var, bool flat, int32_t out[6]) {
-    wf_dispatch(sc, var, flat, false, [&](auto V) {
+void wf_variant(const DevScene& sc, const XKernelCfg& c, int32_t out[6]) {
+    wf_dispatch(sc, c, false, [&](auto V) {
         out[0] = V.lds; out[1] = V.w4; out[2] = V.sh; out[3] = V.tri; out[4] = V.cn; out[5] = V.flat;
     });
 }

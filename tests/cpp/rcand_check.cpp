@@ -1,4 +1,4 @@
-// rcand_check.cpp — CPU check of Mode R's candidate reconstruction (gi_kernels.hip
+// rcand_check.cpp — CPU check of Mode R's candidate reconstruction (gi_mode_r.hip
 // trace_mode_r_cand, host structures from gi_bvh.cpp build_rcand) against the reference-order walk
 // (trace_mode_r: the reverse DFS over the reference octree, first success = the reference's last
 // hitting candidate).  Both are restated here step for step on the host, over libgi's
@@ -21,9 +21,6 @@
 #include "gi.h"
 #include "gi_scene.h"
 
-namespace gi {
-bool build_host_scene(const gi_scene_desc& desc, HostScene& hs, std::string& err);
-}
 using namespace gi;
 
 static uint64_t g_rng = 0x2019abcdULL;

@@ -23,9 +23,6 @@
 #include "gi.h"
 #include "gi_scene.h"
 
-namespace gi {
-bool build_host_scene(const gi_scene_desc& desc, HostScene& hs, std::string& err);
-}
 using namespace gi;
 
 static uint64_t g_rng = 0x2019;
