@@ -66,7 +66,7 @@ STAT_X_IT_RS, STAT_X_LN_RS, STAT_X_IT_ST, STAT_X_LN_ST = 20, 21, 22, 23
 STAT_R_PAIRS, STAT_R_OVF_TILES = 24, 25
 STATS_N = 26
 TILE = 8
-ABI_VERSION = 15
+ABI_VERSION = 16
 RAY_DOUBLES = 8   # a ray record of the batched queries: o[3], d[3], tmax, reserved (gi.h GI_RAY_DOUBLES)
 # the feature buffers of DeviceScene.render_aov (gi.h gi_aov, in its field order): name -> (dtype, trailing shape)
 AOV_OUTPUTS = ("t", "normal", "albedo", "prim", "entity", "uv")
@@ -106,7 +106,8 @@ class SceneInfo(ctypes.Structure):
     _fields_ = [("n_entities", ctypes.c_int32), ("n_nodes", ctypes.c_int32), ("n_leaves", ctypes.c_int32),
                 ("max_depth", ctypes.c_int32), ("n_reachable", ctypes.c_int32), ("n_dropped", ctypes.c_int32),
                 ("x_nodes", ctypes.c_int32), ("x_prims", ctypes.c_int32), ("device_bytes", ctypes.c_int64),
-                ("x_node_bytes", ctypes.c_int32), ("x_lds_resident", ctypes.c_int32)]
+                ("x_node_bytes", ctypes.c_int32), ("x_lds_resident", ctypes.c_int32),
+                ("x_flat_leaves", ctypes.c_int32), ("x_fan_leaves", ctypes.c_int32)]
 
 
 class Hit(ctypes.Structure):

@@ -19,6 +19,7 @@
 #include <string>
 
 #include "gi.h"
+#include "gi_fan_pair.h"
 #include "gi_scene.h"
 
 namespace gi {
@@ -567,6 +568,7 @@ void assign_plane_groups(HostScene& hs) {
 // node's own floats, with its xhot range and plane group.
 void build_xflat(HostScene& hs) {
     hs.xflat.clear();
+    hs.n_fan_leaves = 0;
     bool ok = true;
     for (const XWNode& w : hs.xwnodes) {
         const uint8_t* g = reinterpret_cast<const uint8_t*>(w.pad);
@@ -577,12 +579,15 @@ void build_xflat(HostScene& hs) {
             f.off = ~w.child[c];
             f.cnt = w.cnt[c];
             f.group = g[c];
-            f.pad = 0;
+            // a fan pair (gi_fan_pair.h): the two halves of one planar convex quad, cut along the shared diagonal
+            f.fan = (f.cnt == 2 && fan_pair_ok(hs.xhot[(size_t)f.off], hs.xhot[(size_t)f.off + 1])) ? 1 : 0;
+            hs.n_fan_leaves += f.fan;
             ok = ok && f.cnt <= 255 && f.off < 65536;
             hs.xflat.push_back(f);
         }
     }
     hs.x_flat_ok = ok && hs.xflat.size() <= (size_t)GI_XFLAT_MAX;
+    hs.x_fan_all = !hs.xflat.empty() && (size_t)hs.n_fan_leaves == hs.xflat.size();
 }
 
 bool build_host_scene(const gi_scene_desc& desc, HostScene& hs, std::string& err) {

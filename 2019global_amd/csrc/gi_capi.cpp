@@ -494,6 +494,8 @@ int scene_create_on(const gi_scene_desc* desc, int device, gi_scene** out) {
         // the flat leaf query (gi_wf.hip wf_flat): scenes staged in LDS whose leaf table fits
         d.n_xflat = (int32_t)h.xflat.size();
         d.x_flat = (d.x_lds_bytes > 0 && h.x_flat_ok) ? 1 : 0;
+        // ... and one exact test per fan-pair leaf where its first step decides (gi_fan_pair.h; GI_X_FAN=0: both)
+        d.x_fan = (d.x_flat && h.x_fan_all && x_env().fan) ? 1 : 0;
         // light shading (no acos texture mapping, no sphere primitives): gi_wf.hip's kernels (k_seg, k_cast)
         // run 4 waves per SIMD, provided four workgroups fit a CU's 160 KB.  The bound allows each, beside
         // the scene, 256 lanes x 80 B and 4 x 68 x 4 B -- more than their path slots (256 x 64 B) need: it
@@ -627,6 +629,8 @@ int gi_scene_get_info(const gi_scene* s, gi_scene_info* info) {
     info->device_bytes = s->bytes;
     info->x_node_bytes = s->dev.xcnodes ? (int32_t)sizeof(XCNode) : (int32_t)sizeof(XWNode);
     info->x_lds_resident = s->dev.x_lds_bytes > 0 ? 1 : 0;
+    info->x_flat_leaves = (int32_t)s->host.xflat.size();
+    info->x_fan_leaves = s->host.n_fan_leaves;
     return GI_OK;
 }
 

@@ -913,6 +913,7 @@ const XEnv& x_env() {   // (the knobs: gi_launch.h XEnv)
     std::call_once(once, [] {
         if (const char* v = std::getenv("GI_X_HELP")) env.help = std::atoi(v) != 0;
         if (const char* v = std::getenv("GI_X_FLAT")) env.flat = std::atoi(v) != 0;
+        if (const char* v = std::getenv("GI_X_FAN")) env.fan = std::atoi(v) != 0;
         if (const char* v = std::getenv("GI_SEG_RING")) env.seg_ring = std::atoi(v) != 0;
         if (const char* v = std::getenv("GI_R_FLAT")) env.r_flat = std::atoi(v);
         if (const char* v = std::getenv("GI_RF_PER_SLOT")) env.rf_per_slot = std::max(0, std::min(1024, std::atoi(v)));

@@ -16,11 +16,13 @@ namespace gi {
 // among kernels whose frames are identical bit for bit (tests/test_gpu_parity.py compares them):
 // GI_X_WF (0/1/2: force a Mode X form for a whole suite run), GI_X_HELP=0 (no shadow-ray handoff),
 // GI_X_FLAT=0 (k_seg / k_wf_bounce walk the tree even where the scene's flat leaf table applies),
+// GI_X_FAN=0 (the flat leaf query runs both exact tests of every fan-pair leaf: scenes uploaded by the process
+// get DevScene::x_fan = 0, in the same kernels),
 // GI_SEG_RING=0 (k_seg's lanes make their own units even where the per-wave ring fits),
 // GI_R_FLAT (0/1/2: force a Mode R kernel), GI_RF_PER_SLOT (the flat Mode R pool size: 0 forces the
 // per-tile overflow path), GI_RF_GROUP (1/4: force k_rf_reach's lanes per hit).
 struct XEnv {
-    int run_log2 = 0, help = 1, wf = -1, flat = 1, seg_ring = 1;
+    int run_log2 = 0, help = 1, wf = -1, flat = 1, seg_ring = 1, fan = 1;
     int r_flat = -1;                  // Mode R kernels (GI_R_FLAT): 1 the flat phases for every scene, 0 k_mode_r
                                       // for every scene, 2 k_mode_r_batch for the whole frame (tests); -1 by size
     int rf_per_slot = 16;             // flat Mode R: pool pairs per pixel slot of the frame (GI_RF_PER_SLOT)

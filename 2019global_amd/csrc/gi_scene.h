@@ -151,7 +151,7 @@ struct XFlatLeaf {         // 32 bytes
     int32_t off;           // the leaf's first record in xhot[]
     uint16_t cnt;          // its records
     uint8_t group;         // its plane group (byte c of XWNode::pad; 255 none)
-    uint8_t pad;
+    uint8_t fan;           // 1: its two records are a fan pair (gi_fan_pair.h fan_pair_ok); host-side only
 };
 static_assert(sizeof(XFlatLeaf) == 32, "XFlatLeaf layout");
 
@@ -195,6 +195,9 @@ struct HostScene {
     std::vector<XFlatLeaf> xflat;    // the wide tree's leaf children (build_xflat)
     bool x_flat_ok = false;          // xflat fits the flat query: <= GI_XFLAT_MAX leaves of <= 255 records each,
                                      // offsets below 2^16 (wf_flat packs offset, index and count in a word)
+    int32_t n_fan_leaves = 0;        // leaves of xflat that are fan pairs (XFlatLeaf::fan)
+    bool x_fan_all = false;          // every leaf of xflat is one (and there is a leaf): wf_flat's TRI kernels run
+                                     // one exact test per leaf where the first step decides (DevScene::x_fan)
 };
 // Builds every host structure of a scene from its description (gi_build.cpp); false: err says why.
 bool build_host_scene(const gi_scene_desc& desc, HostScene& hs, std::string& err);
@@ -260,7 +263,11 @@ struct DevScene {
     int32_t x_flat;        // 1: the scene is staged in LDS and its table fits (k_seg / k_wf_bounce use wf_flat)
     float x_far_r;         // 16 x max |coordinate| of root_lo / root_hi (inf: no primitive): rays that start
                            // farther out run their fp32 box tests from a point near the scene (gi_dev.h ray_org32)
+    int32_t x_fan;         // 1: x_flat and every leaf of the table is a fan pair (HostScene::x_fan_all), unless
+                           // GI_X_FAN=0: wf_flat<., true> runs one exact test per leaf where gi_fan_pair.h decides
 };
+// (x_fan fills what was tail padding: the kernels' argument layouts are those of the struct without it)
+static_assert(sizeof(DevScene) == 264, "DevScene layout");
 
 // HIP events bracketing the dominant kernel of renders issued with GI_FLAG_TIME (owned by the
 // scene handle, created on first use): a ring of kRing pairs, so frames stay asynchronous; a pair

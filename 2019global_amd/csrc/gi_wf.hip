@@ -25,6 +25,7 @@
 
 #include "gi.h"
 #include "gi_dev.h"
+#include "gi_fan_pair.h"
 #include "gi_launch.h"
 #include "gi_scene.h"
 #include "gi_seg_ring.h"
@@ -263,9 +264,11 @@ __device__ __forceinline__ bool flat_hit(const XFlatLeaf* r, F3 no, F3 ivf, int 
     pk = flat_pack((uint32_t)b.z, k, (uint32_t)b.w);
     return tn <= tf;
 }
+// fan (launch-uniform, DevScene::x_fan; the TRI kernels): every leaf is a fan pair, phase B runs one exact test per
+// leaf where the first record's first step decides (gi_fan_pair.h) -- the same (t, primitive) as with both
 template <bool ANY, bool TRI>
 __device__ __forceinline__ int wf_flat(float far_r, const XFlatLeaf* tab, const uint32_t* pkw, int n, const XHot* H, V3 o, V3 d, double tmax, bool act,
-                                       double& t_out, uint32_t& nnode, uint32_t& nprim, uint32_t& nsteps, int skip) {
+                                       double& t_out, uint32_t& nnode, uint32_t& nprim, uint32_t& nsteps, int skip, bool fan) {
     const F3 of = ray_org32(o, d, far_r);
     const F3 ivf = inv_dir(d);
     const F3 no = neg_oiv(of, ivf);
@@ -332,6 +335,38 @@ __device__ __forceinline__ int wf_flat(float far_r, const XFlatLeaf* tab, const 
         ++nsteps;
         const int cnt = (int)(pk >> 24);
         const XHot* hp = H + (pk & 0xFFFFu);
+        if (TRI && fan) {
+            // every leaf a fan pair (gi_fan_pair.h): the first record's tv, pv, det and un say which of the
+            // two a ray can hit, and the lane runs that one's exact test; the other's is infinity.  Lanes the
+            // margins leave undecided (rays through the diagonal, grazing rays) run the other record too.
+            const XHotR r0 = load_hot(hp);
+            const int ch = fan_pair_choice(r0.h, o, d);
+            // (the chosen record read again at the lane's address: assembling it from r0 and the second
+            // record's e2 by selects was measured and is slower, C3 2.830-2.841 against 2.821-2.827 ms)
+            const XHotR rc = load_hot(hp + (ch == FAN_T2 ? 1 : 0));
+            const double ta = x_prim_t<TRI>(rc.h, o, d, MX_TMIN);
+            double tq = INFINITY;
+            int pq = rc.h.prim;
+            if (__builtin_amdgcn_ballot_w64(ch == FAN_BOTH) != 0) {
+                if (ch == FAN_BOTH) {
+                    const XHotR r1 = load_hot(hp + 1);
+                    tq = x_prim_t<TRI>(r1.h, o, d, MX_TMIN);
+                    pq = r1.h.prim;
+                }
+            }
+            nprim += 2;   // (records decided)
+            if (ANY) {
+                if ((ta < tmax) | (tq < tmax)) best = ta < tmax ? rc.h.prim : pq;
+            } else {
+                const bool ua = (ta < tb) | ((ta == tb) & (rc.h.prim < best));
+                tb = ua ? ta : tb;
+                best = ua ? rc.h.prim : best;
+                const bool uq = (tq < tb) | ((tq == tb) & (pq < best));
+                tb = uq ? tq : tb;
+                best = uq ? pq : best;
+                tbf = up32(tb);
+            }
+        } else
         for (int j = 0; j < cnt; j += 2) {
             const bool two = j + 1 < cnt;
             const XHotR r0 = load_hot(hp + j), r1 = load_hot(hp + (two ? j + 1 : j));
@@ -509,7 +544,7 @@ __device__ __forceinline__ void wf_wave_steps(uint32_t n, uint64_t& it, uint64_t
 template <bool ANY, bool LDS, bool SH, bool TRI, bool CN, bool FLAT>
 __device__ __forceinline__ int x_query(const DevScene& sc, const WFView& v, float far_r, const V3& o, const V3& d, double tmax,
                                        bool act, double& t_out, uint32_t& nnode, uint32_t& nprim, uint32_t& st_steps, int skip) {
-    if constexpr (FLAT) return wf_flat<ANY, TRI>(far_r, v.FT, v.FP, sc.n_xflat, v.LH, o, d, tmax, act, t_out, nnode, nprim, st_steps, skip);
+    if constexpr (FLAT) return wf_flat<ANY, TRI>(far_r, v.FT, v.FP, sc.n_xflat, v.LH, o, d, tmax, act, t_out, nnode, nprim, st_steps, skip, sc.x_fan != 0);
     else if constexpr (LDS) return wf_trace<ANY, true, false, SH, TRI, false>(far_r, v.LW, v.LH, o, d, tmax, act, v.nst, t_out, nnode, nprim, st_steps, skip);
     else if constexpr (CN) return wf_trace<ANY, false, false, SH, TRI, true>(far_r, sc.xcnodes, sc.xhot, o, d, tmax, act, v.nst, t_out, nnode, nprim, st_steps);
     else return wf_trace<ANY, false, false, SH, TRI, true>(far_r, sc.xwnodes, sc.xhot, o, d, tmax, act, v.nst, t_out, nnode, nprim, st_steps, skip);

@@ -54,7 +54,7 @@
 extern "C" {
 #endif
 
-#define GI_ABI_VERSION 15
+#define GI_ABI_VERSION 16
 
 typedef enum gi_status {
     GI_OK = 0,
@@ -216,6 +216,10 @@ typedef struct gi_scene_info {
     int32_t x_node_bytes;     /* Mode X traversal node record: 256 (XWNode) or 128 (quantised XCNode,
                                  large HBM-resident scenes) -- bench.py's algorithmic bytes per visit */
     int32_t x_lds_resident;   /* 1: Mode X stages the scene in LDS per workgroup */
+    int32_t x_flat_leaves;    /* leaves of the Mode X flat leaf table (ABI 16) */
+    int32_t x_fan_leaves;     /* ... that are fan pairs: the two halves of one planar convex quad, whose
+                                 exact tests the flat query decides between by the first one's first step
+                                 when every leaf is one (ABI 16) */
 } gi_scene_info;
 
 typedef struct gi_hit {
