@@ -22,7 +22,9 @@ one process, RCCL gather; ``RayTracer`` uses it when ``GI_DEVICES`` lists more t
 ``Octree.intersect`` (the reference's public candidate query, on the host).  ``DeviceScene.intersect`` /
 ``occluded`` answer batches of rays; ``DeviceScene.render_aov`` returns a frame's first-hit feature
 buffers (distance, normal, albedo, primitive, entity, texture coordinate) and ``camera_rays`` its pixel
-rays as ray records, each with a ``_device`` form on a HIP stream.
+rays as ray records, each with a ``_device`` form on a HIP stream.  ``denoise`` filters a noisy frame over
+those buffers (an edge-avoiding a-trous filter: a preview of the first progressive passes), with
+``denoise_device`` on a HIP stream into caller-owned buffers.
 """
 from __future__ import annotations
 
@@ -41,6 +43,7 @@ __all__ = [
     "RayTracer", "DeviceScene", "MODE_R", "MODE_X", "STAT_RAYS", "STAT_NODES", "STAT_PRIMS",
     "STAT_PIXELS", "TILE", "MultiScene", "devices_from_env", "obj_entities", "RAY_DOUBLES",
     "AOV_OUTPUTS", "camera_rays", "camera_rays_device",
+    "DenoiseParams", "DENOISE_ALBEDO_STOP", "denoise", "denoise_scratch_bytes", "denoise_device",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -66,7 +69,7 @@ STAT_X_IT_RS, STAT_X_LN_RS, STAT_X_IT_ST, STAT_X_LN_ST = 20, 21, 22, 23
 STAT_R_PAIRS, STAT_R_OVF_TILES = 24, 25
 STATS_N = 26
 TILE = 8
-ABI_VERSION = 16
+ABI_VERSION = 17
 RAY_DOUBLES = 8   # a ray record of the batched queries: o[3], d[3], tmax, reserved (gi.h GI_RAY_DOUBLES)
 # the feature buffers of DeviceScene.render_aov (gi.h gi_aov, in its field order): name -> (dtype, trailing shape)
 AOV_OUTPUTS = ("t", "normal", "albedo", "prim", "entity", "uv")
@@ -125,6 +128,20 @@ class Aov(ctypes.Structure):
                 ("prim", ctypes.c_void_p), ("entity", ctypes.c_void_p), ("uv", ctypes.c_void_p)]
 
 
+DENOISE_ALBEDO_STOP = 1   # gi.h GI_DENOISE_ALBEDO_STOP
+DENOISE_OUTPUTS = ("rgb", "rgb8")
+
+
+class DenoiseParams(ctypes.Structure):
+    _fields_ = [("levels", ctypes.c_int32), ("normal_pow_log2", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("reserved", ctypes.c_int32), ("sigma_c", ctypes.c_double), ("sigma_p", ctypes.c_double)]
+
+
+class DenoiseIO(ctypes.Structure):
+    _fields_ = [("rgb", ctypes.c_void_p), ("t", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("albedo", ctypes.c_void_p),
+                ("out_rgb", ctypes.c_void_p), ("out_rgb8", ctypes.c_void_p)]
+
+
 TILE_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint8),
                            ctypes.POINTER(ctypes.c_double))
 
@@ -133,7 +150,8 @@ EXPORTS = ["gi_abi_version", "gi_last_error", "gi_camera_init", "gi_scene_create
            "gi_trace_ray", "gi_kat_expbox", "gi_kat_x_query", "gi_kat_x_variant", "gi_kat_x_texel", "gi_scene_kernel_ms", "gi_scene_x_form", "gi_scene_seg_ring", "gi_scene_r_kernel", "gi_octree_create", "gi_octree_destroy",
            "gi_octree_intersect", "gi_multi_create", "gi_multi_destroy", "gi_multi_info", "gi_multi_render", "gi_device_count",
            "gi_device_list", "gi_build_id", "gi_obj_parse", "gi_intersect", "gi_occluded", "gi_intersect_device",
-           "gi_occluded_device", "gi_render_aov", "gi_render_aov_device", "gi_camera_rays", "gi_camera_rays_device"]
+           "gi_occluded_device", "gi_render_aov", "gi_render_aov_device", "gi_camera_rays", "gi_camera_rays_device",
+           "gi_denoise_scratch_bytes", "gi_denoise_device", "gi_denoise"]
 
 _lib = None
 _lock = threading.Lock()
@@ -182,6 +200,12 @@ def lib():
         L.gi_render_aov_device.argtypes = [vp, ctypes.POINTER(CameraDesc), ctypes.POINTER(AovFrame), ctypes.POINTER(Aov), vp]
         L.gi_camera_rays.argtypes = [ctypes.POINTER(CameraDesc), ctypes.POINTER(AovFrame), dp]
         L.gi_camera_rays_device.argtypes = [ctypes.POINTER(CameraDesc), ctypes.POINTER(AovFrame), vp, vp]
+        L.gi_denoise_scratch_bytes.argtypes = [ctypes.POINTER(AovFrame), ctypes.POINTER(DenoiseParams)]
+        L.gi_denoise_scratch_bytes.restype = ctypes.c_int64
+        L.gi_denoise_device.argtypes = [ctypes.POINTER(CameraDesc), ctypes.POINTER(AovFrame), ctypes.POINTER(DenoiseParams),
+                                        ctypes.POINTER(DenoiseIO), vp, ctypes.c_int64, vp]
+        L.gi_denoise.argtypes = [ctypes.POINTER(CameraDesc), ctypes.POINTER(AovFrame), ctypes.POINTER(DenoiseParams),
+                                 ctypes.POINTER(DenoiseIO)]
         L.gi_scene_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)]
         L.gi_scene_x_form.argtypes = [vp, ctypes.POINTER(Opts), ctypes.POINTER(ctypes.c_int32)]
         L.gi_scene_seg_ring.argtypes = [vp, ctypes.POINTER(Opts), ctypes.POINTER(ctypes.c_int32)]
@@ -736,6 +760,69 @@ def camera_rays_device(cam: "Camera", w: int, h: int, d_rays: int, window=None, 
     f = _aov_frame(w, h, window)
     _check(lib().gi_camera_rays_device(ctypes.byref(cam._c), ctypes.byref(f), d_rays or None, stream or None),
            "gi_camera_rays_device")
+
+
+def _denoise_params(levels, sigma_c, sigma_p, normal_pow_log2, albedo_stop) -> DenoiseParams:
+    return DenoiseParams(int(levels), int(normal_pow_log2), DENOISE_ALBEDO_STOP if albedo_stop else 0, 0, float(sigma_c),
+                         float(sigma_p))
+
+
+def denoise_scratch_bytes(w: int, h: int, window=None, levels: int = 4, sigma_c: float = 0.25, sigma_p: float = 0.01,
+                          normal_pow_log2: int = 5, albedo_stop: bool = True) -> int:
+    """The bytes of device scratch denoise_device needs for this window and these parameters
+    (gi_denoise_scratch_bytes; host code, no device)."""
+    f = _aov_frame(w, h, window)
+    p = _denoise_params(levels, sigma_c, sigma_p, normal_pow_log2, albedo_stop)
+    n = lib().gi_denoise_scratch_bytes(ctypes.byref(f), ctypes.byref(p))
+    if n < 0:
+        _check(int(n), "gi_denoise_scratch_bytes")
+    return int(n)
+
+
+def denoise(cam: "Camera", w: int, h: int, rgb, t, normal, albedo=None, window=None, levels: int = 4, sigma_c: float = 0.25,
+            sigma_p: float = 0.01, normal_pow_log2: int = 5, albedo_stop: bool = True, want=DENOISE_OUTPUTS) -> dict:
+    """The edge-avoiding a-trous filter of gi.h "denoiser" over the window (x0, y0, x1, y1) of a w x h frame
+    (None: the whole frame), from host arrays (gi_denoise): rgb (rows, cols, 3), and render_aov's t (rows, cols),
+    normal and albedo (rows, cols, 3) for the same camera and window, float64; albedo may be None without
+    albedo_stop.  sigma_c: about 0.5 / sqrt(samples accumulated so far).  Returns the outputs named in want:
+    "rgb" (rows, cols, 3) float64, "rgb8" (rows, cols, 3) uint8.  ValueError for a wrong shape or want."""
+    want = tuple(want)
+    if not want or any(k not in DENOISE_OUTPUTS for k in want) or len(set(want)) != len(want):
+        raise ValueError(f"denoise: want is a non-empty selection of {DENOISE_OUTPUTS}")
+    f = _aov_frame(w, h, window)
+    rows, cols = f.y1 - f.y0, f.x1 - f.x0
+    if albedo is None and albedo_stop:
+        raise ValueError("denoise: albedo_stop needs the albedo plane")
+
+    def plane(name, a, tail):
+        a = np.ascontiguousarray(a, np.float64)
+        if a.size != rows * cols * (tail[0] if tail else 1):
+            raise ValueError(f"denoise: {name} must hold {(rows, cols) + tail} float64")
+        return a
+    ins = {"rgb": plane("rgb", rgb, (3,)), "t": plane("t", t, ()), "normal": plane("normal", normal, (3,))}
+    if albedo is not None:
+        ins["albedo"] = plane("albedo", albedo, (3,))
+    bufs = {"rgb": np.empty((rows, cols, 3), np.float64), "rgb8": np.empty((rows, cols, 3), np.uint8)}
+    io = DenoiseIO(**{k: (a.ctypes.data if a.size else _scratch_ptr()) for k, a in ins.items()},
+                   # (an empty window: valid addresses, the outputs' apart from the inputs' -- out_rgb is not rgb)
+                   **{"out_" + k: (bufs[k].ctypes.data if bufs[k].size else _scratch_ptr() + 32) for k in want})
+    p = _denoise_params(levels, sigma_c, sigma_p, normal_pow_log2, albedo_stop)
+    _check(lib().gi_denoise(ctypes.byref(cam._c), ctypes.byref(f), ctypes.byref(p), ctypes.byref(io)), "gi_denoise")
+    return {k: bufs[k] for k in want}
+
+
+def denoise_device(cam: "Camera", w: int, h: int, d_rgb: int, d_t: int, d_normal: int, d_albedo: int, d_scratch: int,
+                   scratch_bytes: int, d_out_rgb: int = 0, d_out_rgb8: int = 0, window=None, levels: int = 4,
+                   sigma_c: float = 0.25, sigma_p: float = 0.01, normal_pow_log2: int = 5, albedo_stop: bool = True,
+                   stream: int = 0) -> None:
+    """Asynchronous denoise of device planes into device outputs on the current device (gi_denoise_device);
+    pointers are ints, an output of 0 is not written.  d_scratch: scratch_bytes >= denoise_scratch_bytes(...)
+    bytes of device memory, 16-byte aligned, the call's own until its launches have run."""
+    f = _aov_frame(w, h, window)
+    io = DenoiseIO(d_rgb or None, d_t or None, d_normal or None, d_albedo or None, d_out_rgb or None, d_out_rgb8 or None)
+    p = _denoise_params(levels, sigma_c, sigma_p, normal_pow_log2, albedo_stop)
+    _check(lib().gi_denoise_device(ctypes.byref(cam._c), ctypes.byref(f), ctypes.byref(p), ctypes.byref(io), d_scratch or None,
+                                   int(scratch_bytes), stream or None), "gi_denoise_device")
 
 
 def devices_from_env(default=None):

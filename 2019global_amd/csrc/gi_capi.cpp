@@ -927,15 +927,20 @@ int gi_occluded(gi_scene* s, int64_t n, const double* rays, int32_t* occluded) {
 // ordering against the scene's renders, nothing of the progressive-frame state is touched.
 namespace {
 // the frame, its window and the camera of an AOV / camera-ray call; *empty: the window holds no pixel
-int check_aov_frame(const gi_camera* cam, const gi_aov_frame* f, bool* empty) {
-    if (!cam || !f) return fail(GI_ERR_ARG, "null camera or frame");
+int check_frame_window(const gi_aov_frame* f, bool* empty) {
     if (f->w <= 0 || f->h <= 0 || (int64_t)f->w * f->h > (int64_t)1 << 34) return fail(GI_ERR_ARG, "bad frame size");
     if (f->x0 < 0 || f->y0 < 0 || f->x1 > f->w || f->y1 > f->h || f->x0 > f->x1 || f->y0 > f->y1)
         return fail(GI_ERR_ARG, "the window [x0, x1) x [y0, y1) is reversed or not inside the frame");
+    *empty = f->x0 == f->x1 || f->y0 == f->y1;
+    return GI_OK;
+}
+int check_aov_frame(const gi_camera* cam, const gi_aov_frame* f, bool* empty) {
+    if (!cam || !f) return fail(GI_ERR_ARG, "null camera or frame");
+    const int rc = check_frame_window(f, empty);
+    if (rc) return rc;
     bool fin = std::isfinite(cam->focal);
     for (int k = 0; k < 3; ++k) fin = fin && std::isfinite(cam->pos[k]) && std::isfinite(cam->up[k]) && std::isfinite(cam->forward[k]);
     if (!fin) return fail(GI_ERR_ARG, "non-finite camera field");
-    *empty = f->x0 == f->x1 || f->y0 == f->y1;
     return GI_OK;
 }
 bool aov_all_null(const gi_aov& a) { return !a.t && !a.normal && !a.albedo && !a.prim && !a.entity && !a.uv; }
@@ -1024,6 +1029,91 @@ int gi_camera_rays(const gi_camera* cam, const gi_aov_frame* frame, double* rays
                             static_cast<double*>(dr.p), nullptr);
         if (e == hipSuccess) e = hipMemcpy(rays, dr.p, bytes, hipMemcpyDeviceToHost);
         return e == hipSuccess ? GI_OK : hip_fail(e, "gi_camera_rays");
+    });
+}
+
+// ---- denoiser (gi.h "denoiser"; gi_denoise.hip k_dn_prep, k_dn_level) ----
+// No scene and no state: the caller's planes and scratch on the current device.
+namespace {
+int check_denoise_params(const gi_denoise_params* p) {
+    if (!p) return fail(GI_ERR_ARG, "null denoise parameters");
+    if (p->levels < 1 || p->levels > 8) return fail(GI_ERR_ARG, "gi_denoise: levels outside 1..8");
+    if (p->normal_pow_log2 < 0 || p->normal_pow_log2 > 7) return fail(GI_ERR_ARG, "gi_denoise: normal_pow_log2 outside 0..7");
+    if (p->flags & ~GI_DENOISE_ALBEDO_STOP) return fail(GI_ERR_ARG, "gi_denoise: unknown flag");
+    if (p->reserved != 0) return fail(GI_ERR_ARG, "gi_denoise: reserved must be 0");
+    if (!(p->sigma_c > 0) || !(p->sigma_p > 0)) return fail(GI_ERR_ARG, "gi_denoise: sigma_c and sigma_p must be > 0 (+inf: no stop)");
+    return GI_OK;
+}
+// everything of a denoise call but the scratch; *empty: the window holds no pixel
+int check_denoise(const gi_camera* cam, const gi_aov_frame* frame, const gi_denoise_params* p, const gi_denoise_io* io, bool* empty) {
+    if (!io) return fail(GI_ERR_ARG, "null denoise io");
+    int rc = check_aov_frame(cam, frame, empty);
+    if (rc || (rc = check_denoise_params(p))) return rc;
+    if (!io->rgb || !io->t || !io->normal) return fail(GI_ERR_ARG, "gi_denoise: null rgb, t or normal");
+    if (!io->out_rgb && !io->out_rgb8) return fail(GI_ERR_ARG, "gi_denoise: both outputs are null");
+    if ((p->flags & GI_DENOISE_ALBEDO_STOP) && !io->albedo) return fail(GI_ERR_ARG, "gi_denoise: the albedo stop needs the albedo plane");
+    if (io->out_rgb == io->rgb) return fail(GI_ERR_ARG, "gi_denoise: out_rgb must not be rgb");
+    return GI_OK;
+}
+int64_t denoise_bytes(const gi_aov_frame& f, const gi_denoise_params& p) {
+    return dn_scratch_bytes((long long)(f.x1 - f.x0) * (long long)(f.y1 - f.y0), p.levels, (p.flags & GI_DENOISE_ALBEDO_STOP) != 0);
+}
+DnIO dn_io(const gi_aov_frame& f, const gi_denoise_io& d) {
+    return DnIO{f.x0, f.y0, f.x1 - f.x0, f.y1 - f.y0, d.rgb, d.t, d.normal, d.albedo, d.out_rgb, d.out_rgb8};
+}
+}  // namespace
+
+int64_t gi_denoise_scratch_bytes(const gi_aov_frame* frame, const gi_denoise_params* p) {   // (nothing here can throw)
+    if (!frame) return fail(GI_ERR_ARG, "null frame");
+    bool empty = false;
+    int rc = check_frame_window(frame, &empty);
+    if (rc || (rc = check_denoise_params(p))) return rc;
+    return empty ? 0 : denoise_bytes(*frame, *p);
+}
+
+int gi_denoise_device(const gi_camera* cam, const gi_aov_frame* frame, const gi_denoise_params* p, const gi_denoise_io* d_io,
+                      void* d_scratch, int64_t scratch_bytes, void* stream) {
+    return guard([&]() -> int {
+        bool empty = false;
+        const int rc = check_denoise(cam, frame, p, d_io, &empty);
+        if (rc) return rc;
+        if (scratch_bytes < (empty ? 0 : denoise_bytes(*frame, *p))) return fail(GI_ERR_ARG, "gi_denoise: scratch_bytes below gi_denoise_scratch_bytes");
+        if (empty) return GI_OK;
+        if (!d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 15)) return fail(GI_ERR_ARG, "gi_denoise: the device scratch must be non-null and 16-byte aligned");
+        const hipError_t e = launch_denoise(make_cam(*cam, frame->w), dn_io(*frame, *d_io), *p, d_scratch, static_cast<hipStream_t>(stream));
+        return e == hipSuccess ? GI_OK : hip_fail(e, "gi_denoise launch");
+    });
+}
+
+int gi_denoise(const gi_camera* cam, const gi_aov_frame* frame, const gi_denoise_params* p, const gi_denoise_io* io) {
+    return guard([&]() -> int {
+        bool empty = false;
+        const int rc = check_denoise(cam, frame, p, io, &empty);
+        if (rc) return rc;
+        if (empty) return GI_OK;
+        const size_t m = (size_t)(frame->x1 - frame->x0) * (size_t)(frame->y1 - frame->y0);
+        const bool stop = (p->flags & GI_DENOISE_ALBEDO_STOP) != 0;
+        DevBuf drgb, dt, dn, da, dout, dout8, dscr;
+        hipError_t e = drgb.alloc(m * 3 * sizeof(double));
+        if (e == hipSuccess) e = dt.alloc(m * sizeof(double));
+        if (e == hipSuccess) e = dn.alloc(m * 3 * sizeof(double));
+        if (e == hipSuccess && stop) e = da.alloc(m * 3 * sizeof(double));
+        if (e == hipSuccess && io->out_rgb) e = dout.alloc(m * 3 * sizeof(double));
+        if (e == hipSuccess && io->out_rgb8) e = dout8.alloc(m * 3);
+        if (e == hipSuccess) e = dscr.alloc((size_t)denoise_bytes(*frame, *p));
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc (denoiser staging)");
+        e = hipMemcpy(drgb.p, io->rgb, m * 3 * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(dt.p, io->t, m * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(dn.p, io->normal, m * 3 * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess && stop) e = hipMemcpy(da.p, io->albedo, m * 3 * sizeof(double), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return hip_fail(e, "gi_denoise");
+        const gi_denoise_io d{static_cast<const double*>(drgb.p), static_cast<const double*>(dt.p), static_cast<const double*>(dn.p),
+                              static_cast<const double*>(da.p), static_cast<double*>(dout.p), static_cast<uint8_t*>(dout8.p)};
+        e = launch_denoise(make_cam(*cam, frame->w), dn_io(*frame, d), *p, dscr.p, nullptr);
+        if (e != hipSuccess) return hip_fail(e, "gi_denoise launch");
+        if (io->out_rgb) e = hipMemcpy(io->out_rgb, dout.p, m * 3 * sizeof(double), hipMemcpyDeviceToHost);   // (synchronous copies on the launch's stream)
+        if (e == hipSuccess && io->out_rgb8) e = hipMemcpy(io->out_rgb8, dout8.p, m * 3, hipMemcpyDeviceToHost);
+        return e == hipSuccess ? GI_OK : hip_fail(e, "gi_denoise");
     });
 }
 

@@ -1,4 +1,4 @@
-// gi_launch.h — the host functions that libgi's kernel units (gi_kernels.hip, gi_mode_r.hip, gi_wf.hip)
+// gi_launch.h — the host functions that libgi's kernel units (gi_kernels.hip, gi_mode_r.hip, gi_wf.hip, gi_denoise.hip)
 // define for each other and for gi_capi.cpp.  The only place where a cross-unit function is declared: the
 // unit that defines one and the units that call it all include this header.  Host-only, no device code.
 #pragma once
@@ -84,5 +84,18 @@ hipError_t launch_cast(const DevScene& sc, const XKernelCfg& c, bool any, const 
 hipError_t launch_aov(const DevScene& sc, const XKernelCfg& c, const CamDev& cam, const AovIO& io, hipStream_t stream);
 hipError_t launch_cam_rays(const CamDev& cam, int x0, int y0, int cols, int rows, double* rays, hipStream_t stream);
 void wf_variant(const DevScene& sc, const XKernelCfg& c, int32_t out[6]);
+
+// ---- gi_denoise.hip: k_dn_prep, k_dn_level ----
+// One call of the denoiser (gi_denoise*): the window [x0, x0 + cols) x [y0, y0 + rows) of the frame, its
+// input planes and outputs, device pointers, row-major over the window; alb is read only with the albedo
+// stop; a null output is not written.
+struct DnIO {
+    int x0, y0, cols, rows;
+    const double *rgb, *t, *nrm, *alb;
+    double* out;
+    uint8_t* out8;
+};
+long long dn_scratch_bytes(long long n_px, int levels, bool albedo_stop);   // host only
+hipError_t launch_denoise(const CamDev& cam, const DnIO& io, const gi_denoise_params& p, void* scratch, hipStream_t stream);
 
 }  // namespace gi

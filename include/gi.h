@@ -22,6 +22,8 @@
  *                        albedo, primitive, entity, texture coordinate (no reference counterpart)
  *   gi_camera_rays*      a frame's pixel rays (raytracer.h:41-43) as ray records for gi_intersect* /
  *                        gi_occluded*
+ *   gi_denoise*          an edge-avoiding a-trous filter of a frame over those feature buffers: a preview of
+ *                        the first progressive passes (no reference counterpart)
  *   gi_unshard_device    reassembles a frame from per-rank packed tiles after the RCCL gather
  *   gi_scene_kernel_ms   HIP-event duration of the last timed render's dominant kernel (bench)
  *   gi_scene_x_form      which Mode X form (persistent kernel / wavefront) a render would run
@@ -54,7 +56,7 @@
 extern "C" {
 #endif
 
-#define GI_ABI_VERSION 16
+#define GI_ABI_VERSION 17
 
 typedef enum gi_status {
     GI_OK = 0,
@@ -369,6 +371,72 @@ int gi_render_aov_device(gi_scene* scene, const gi_camera* cam, const gi_aov_fra
 int gi_render_aov(gi_scene* scene, const gi_camera* cam, const gi_aov_frame* frame, const gi_aov* out);
 int gi_camera_rays_device(const gi_camera* cam, const gi_aov_frame* frame, double* d_rays, void* stream);
 int gi_camera_rays(const gi_camera* cam, const gi_aov_frame* frame, double* rays);
+
+/* ---- denoiser: an edge-avoiding a-trous filter over the feature buffers (ABI 17) ----------------
+ * A preview of a noisy frame -- the first passes of a progressive Mode X frame -- from the frame and the
+ * t, normal and albedo planes of gi_render_aov* for the same camera and window.  No scene: like
+ * gi_camera_rays* the calls run on the current HIP device.  All planes are row-major over the window
+ * [x0, x1) x [y0, y1) of the w x h frame; the camera and the frame are needed because the plane stop
+ * uses the pixels' hit positions.
+ *
+ * The filter, exactly.  Everything is fp64, no operation is contracted, dots are summed as
+ * (x x' + y y') + z z'.  Per valid pixel p (t_p < +inf) at absolute pixel (x, y):
+ *   d_p = normalize(primary_dir(cam, x, y))  (gi_camera_rays' d),  P_p = cam.pos + t_p d_p (per component
+ *   one multiply, then one add),  s_p = sigma_p t_p,  c^0 = rgb.
+ * Level i = 0 .. levels-1 has step s = 2^i and sigma2 = (sigma_c 2^-i)^2 (ldexp, then one multiply):
+ *   sum_w = 0; sum_c = (0, 0, 0)
+ *   for dy = -2..2 (outer), dx = -2..2 (inner), sums sequential in this order:
+ *       q = p + s (dx, dy); skipped if q is outside the window, or invalid, or (GI_DENOISE_ALBEDO_STOP and
+ *                           not albedo_q == albedo_p in all three doubles)
+ *       k   = H[dx+2] H[dy+2],  H = {1/16, 1/4, 3/8, 1/4, 1/16}
+ *       w_n = max(n_p . n_q, 0), squared normal_pow_log2 times
+ *       w_p = max(1 - |n_p . (P_q - P_p)| / s_p, 0)
+ *       e   = c_p - c_q;  w_c = 1 / (1 + ((e.r e.r + e.g e.g) + e.b e.b) / sigma2)
+ *       wt  = ((k w_n) w_p) w_c;  sum_w += wt;  sum_c += wt c_q
+ *   c^{i+1}_p = sum_c / sum_w        (the centre tap always counts)
+ * max(v, 0) is v > 0 ? v : 0.  Invalid pixels (t = +inf) pass through every level unchanged and are never
+ * taps.  After the last level out_rgb = min(c, 1) (c < 1 ? c : 1) and out_rgb8 = quantize(out_rgb), the
+ * frames' (int)(255 c).  No transcendental function appears: a restatement with the same order is exact.
+ *
+ * The caller's planes are trusted: a non-finite value in a valid pixel (or a t <= 0, a normal that is
+ * not a unit vector) gives unspecified pixels, never a fault.
+ * sigma_c: about 0.5 / sqrt(samples accumulated so far) (README.md "Denoiser").
+ * The _device form takes device pointers and is asynchronous on `stream` (hipStream_t; NULL = default
+ * stream): it makes no allocation, no copy and no host synchronisation; the caller owns the scratch
+ * (gi_denoise_scratch_bytes bytes, 16-byte aligned), which no other work may use until the call's
+ * launches have run.  gi_denoise does the same from / into host buffers (stage, launch, copy back) and
+ * is synchronous.
+ *   Arguments  GI_ERR_ARG for a NULL cam, frame, p or io; a NULL rgb, t or normal; both outputs NULL; a
+ *              NULL albedo with GI_DENOISE_ALBEDO_STOP; levels outside 1..8, normal_pow_log2 outside 0..7,
+ *              a sigma_c or sigma_p that is not > 0 (NaN included; +inf is allowed), an unknown flag, a
+ *              non-zero reserved; a bad frame or window and a camera with a non-finite field, as
+ *              gi_render_aov judges them; out_rgb equal to rgb; scratch_bytes below
+ *              gi_denoise_scratch_bytes, a NULL or not 16-byte aligned device scratch.  An empty window
+ *              launches nothing and returns GI_OK.  gi_denoise_scratch_bytes (host only, no device): the
+ *              bytes, or a negative gi_status for a bad frame or parameters (0 for an empty window).
+ * Not provided: temporal accumulation, variance-guided sigmas, albedo demodulation, Mode R frames,
+ * shard-packed buffers / gi_multi. */
+#define GI_DENOISE_ALBEDO_STOP 1u  /* a tap contributes only if its albedo equals the centre's (three fp64 ==) */
+typedef struct gi_denoise_params {
+    int32_t levels;           /* 1..8 a-trous levels, level i has step 2^i */
+    int32_t normal_pow_log2;  /* 0..7: w_n = max(n_p.n_q, 0)^(2^k), by k squarings */
+    uint32_t flags;           /* GI_DENOISE_* */
+    int32_t reserved;         /* 0 */
+    double sigma_c;           /* > 0, +inf = no colour stop; level i uses sigma_c * 2^-i */
+    double sigma_p;           /* > 0, +inf = no plane stop; plane distance in units of the centre's t */
+} gi_denoise_params;
+typedef struct gi_denoise_io {
+    const double* rgb;        /* rows*cols*3: the frame to filter (gi_render_device's layout over the window) */
+    const double* t;          /* rows*cols: gi_aov.t; a pixel is valid iff t < +inf */
+    const double* normal;     /* rows*cols*3: gi_aov.normal */
+    const double* albedo;     /* rows*cols*3: gi_aov.albedo; may be NULL without GI_DENOISE_ALBEDO_STOP */
+    double* out_rgb;          /* rows*cols*3, may be NULL */
+    uint8_t* out_rgb8;        /* rows*cols*3, may be NULL; quantize() of out_rgb (gi_math.h) */
+} gi_denoise_io;
+int64_t gi_denoise_scratch_bytes(const gi_aov_frame* frame, const gi_denoise_params* p);
+int gi_denoise_device(const gi_camera* cam, const gi_aov_frame* frame, const gi_denoise_params* p,
+                      const gi_denoise_io* d_io, void* d_scratch, int64_t scratch_bytes, void* stream);
+int gi_denoise(const gi_camera* cam, const gi_aov_frame* frame, const gi_denoise_params* p, const gi_denoise_io* io);
 
 /* Average duration in ms of the dominant kernel over the scene's renders issued with GI_FLAG_TIME
  * since the previous call (waits for the last one; *n = how many, may be NULL), then resets.
