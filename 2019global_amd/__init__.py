@@ -24,7 +24,9 @@ one process, RCCL gather; ``RayTracer`` uses it when ``GI_DEVICES`` lists more t
 buffers (distance, normal, albedo, primitive, entity, texture coordinate) and ``camera_rays`` its pixel
 rays as ray records, each with a ``_device`` form on a HIP stream.  ``denoise`` filters a noisy frame over
 those buffers (an edge-avoiding a-trous filter: a preview of the first progressive passes), with
-``denoise_device`` on a HIP stream into caller-owned buffers.
+``denoise_device`` on a HIP stream into caller-owned buffers.  ``DeviceScene.frame_moments`` returns the
+per-pixel sample mean, variance of the mean and per-sample radiance of the scene's retained Mode X frame, and
+``denoise_var`` is the filter with its colour stop per pixel from that variance (``_device`` forms alike).
 """
 from __future__ import annotations
 
@@ -44,6 +46,8 @@ __all__ = [
     "STAT_PIXELS", "TILE", "MultiScene", "devices_from_env", "obj_entities", "RAY_DOUBLES",
     "AOV_OUTPUTS", "camera_rays", "camera_rays_device",
     "DenoiseParams", "DENOISE_ALBEDO_STOP", "denoise", "denoise_scratch_bytes", "denoise_device",
+    "MOMENTS_OUTPUTS", "DenoiseVarParams", "DENOISE_VAR_OUTPUTS", "DENOISE_VAR_SIGMA_V", "DENOISE_VAR_FLOOR",
+    "denoise_var", "denoise_var_scratch_bytes", "denoise_var_device",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -69,7 +73,7 @@ STAT_X_IT_RS, STAT_X_LN_RS, STAT_X_IT_ST, STAT_X_LN_ST = 20, 21, 22, 23
 STAT_R_PAIRS, STAT_R_OVF_TILES = 24, 25
 STATS_N = 26
 TILE = 8
-ABI_VERSION = 17
+ABI_VERSION = 18
 RAY_DOUBLES = 8   # a ray record of the batched queries: o[3], d[3], tmax, reserved (gi.h GI_RAY_DOUBLES)
 # the feature buffers of DeviceScene.render_aov (gi.h gi_aov, in its field order): name -> (dtype, trailing shape)
 AOV_OUTPUTS = ("t", "normal", "albedo", "prim", "entity", "uv")
@@ -142,6 +146,31 @@ class DenoiseIO(ctypes.Structure):
                 ("out_rgb", ctypes.c_void_p), ("out_rgb8", ctypes.c_void_p)]
 
 
+MOMENTS_OUTPUTS = ("mean", "var", "samples")   # gi.h gi_moments, in its field order
+
+
+class Moments(ctypes.Structure):
+    _fields_ = [("mean", ctypes.c_void_p), ("var", ctypes.c_void_p), ("samples", ctypes.c_void_p)]
+
+
+DENOISE_VAR_OUTPUTS = ("rgb", "var", "rgb8")
+# denoise_var's defaults, chosen by a sweep over the first passes of the Cornell box (DESIGN.md §9 "Denoiser")
+DENOISE_VAR_SIGMA_V = 1.0
+DENOISE_VAR_FLOOR = 1e-6
+
+
+class DenoiseVarParams(ctypes.Structure):
+    _fields_ = [("levels", ctypes.c_int32), ("normal_pow_log2", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("reserved", ctypes.c_int32), ("sigma_v", ctypes.c_double), ("sigma_p", ctypes.c_double),
+                ("var_floor", ctypes.c_double)]
+
+
+class DenoiseVarIO(ctypes.Structure):
+    _fields_ = [("rgb", ctypes.c_void_p), ("var", ctypes.c_void_p), ("t", ctypes.c_void_p), ("normal", ctypes.c_void_p),
+                ("albedo", ctypes.c_void_p), ("out_rgb", ctypes.c_void_p), ("out_var", ctypes.c_void_p),
+                ("out_rgb8", ctypes.c_void_p)]
+
+
 TILE_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint8),
                            ctypes.POINTER(ctypes.c_double))
 
@@ -151,7 +180,9 @@ EXPORTS = ["gi_abi_version", "gi_last_error", "gi_camera_init", "gi_scene_create
            "gi_octree_intersect", "gi_multi_create", "gi_multi_destroy", "gi_multi_info", "gi_multi_render", "gi_device_count",
            "gi_device_list", "gi_build_id", "gi_obj_parse", "gi_intersect", "gi_occluded", "gi_intersect_device",
            "gi_occluded_device", "gi_render_aov", "gi_render_aov_device", "gi_camera_rays", "gi_camera_rays_device",
-           "gi_denoise_scratch_bytes", "gi_denoise_device", "gi_denoise"]
+           "gi_denoise_scratch_bytes", "gi_denoise_device", "gi_denoise",
+           "gi_frame_samples_info", "gi_frame_moments_device", "gi_frame_moments",
+           "gi_denoise_var_scratch_bytes", "gi_denoise_var_device", "gi_denoise_var"]
 
 _lib = None
 _lock = threading.Lock()
@@ -206,6 +237,15 @@ def lib():
                                         ctypes.POINTER(DenoiseIO), vp, ctypes.c_int64, vp]
         L.gi_denoise.argtypes = [ctypes.POINTER(CameraDesc), ctypes.POINTER(AovFrame), ctypes.POINTER(DenoiseParams),
                                  ctypes.POINTER(DenoiseIO)]
+        L.gi_frame_samples_info.argtypes = [vp, ip, ip, ip, ip]
+        L.gi_frame_moments_device.argtypes = [vp, ctypes.POINTER(AovFrame), ctypes.POINTER(Moments), vp]
+        L.gi_frame_moments.argtypes = [vp, ctypes.POINTER(AovFrame), ctypes.POINTER(Moments)]
+        L.gi_denoise_var_scratch_bytes.argtypes = [ctypes.POINTER(AovFrame), ctypes.POINTER(DenoiseVarParams)]
+        L.gi_denoise_var_scratch_bytes.restype = ctypes.c_int64
+        L.gi_denoise_var_device.argtypes = [ctypes.POINTER(CameraDesc), ctypes.POINTER(AovFrame), ctypes.POINTER(DenoiseVarParams),
+                                            ctypes.POINTER(DenoiseVarIO), vp, ctypes.c_int64, vp]
+        L.gi_denoise_var.argtypes = [ctypes.POINTER(CameraDesc), ctypes.POINTER(AovFrame), ctypes.POINTER(DenoiseVarParams),
+                                     ctypes.POINTER(DenoiseVarIO)]
         L.gi_scene_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)]
         L.gi_scene_x_form.argtypes = [vp, ctypes.POINTER(Opts), ctypes.POINTER(ctypes.c_int32)]
         L.gi_scene_seg_ring.argtypes = [vp, ctypes.POINTER(Opts), ctypes.POINTER(ctypes.c_int32)]
@@ -687,6 +727,38 @@ class DeviceScene:
         _check(lib().gi_render_aov_device(self._h, ctypes.byref(cam._c), ctypes.byref(f), ctypes.byref(a), stream or None),
                "gi_render_aov_device")
 
+    # ---- sample moments of the retained frame (gi.h "sample moments") ---------------------------------
+    def frame_samples_info(self) -> dict:
+        """The retained frame -- the scene's last render, if it was a whole Mode X frame with spp > 1 on one shard:
+        {"w", "h", "n" (samples rendered so far), "spp"} (gi_frame_samples_info); GIError without one."""
+        v = [ctypes.c_int32() for _ in range(4)]
+        _check(lib().gi_frame_samples_info(self._h, *(ctypes.byref(x) for x in v)), "gi_frame_samples_info")
+        return dict(zip(("w", "h", "n", "spp"), (int(x.value) for x in v)))
+
+    def frame_moments(self, w: int, h: int, window=None, want=("mean", "var")) -> dict:
+        """Per-pixel sample moments of the retained w x h frame over the window (x0, y0, x1, y1) (None: the whole
+        frame), gi_frame_moments: the outputs named in want, float64 -- "mean" (rows, cols, 3), min(mean, 1) being
+        the delivered frame; "var" (rows, cols, 3), the sample variance of the mean; "samples" (rows, cols, n, 3),
+        the per-sample radiance itself.  ValueError for an unknown, repeated or empty want or a bad window."""
+        want = tuple(want)
+        if not want or any(k not in MOMENTS_OUTPUTS for k in want) or len(set(want)) != len(want):
+            raise ValueError(f"frame_moments: want is a non-empty selection of {MOMENTS_OUTPUTS}")
+        f = _aov_frame(w, h, window)
+        rows, cols = f.y1 - f.y0, f.x1 - f.x0
+        n = self.frame_samples_info()["n"] if "samples" in want else 0
+        bufs = {k: np.empty((rows, cols, n, 3) if k == "samples" else (rows, cols, 3), np.float64) for k in want}
+        m = Moments(**{k: bufs[k].ctypes.data if bufs[k].size else _scratch_ptr() for k in want})
+        _check(lib().gi_frame_moments(self._h, ctypes.byref(f), ctypes.byref(m)), "gi_frame_moments")
+        return bufs
+
+    def frame_moments_device(self, w: int, h: int, window=None, d_mean: int = 0, d_var: int = 0, d_samples: int = 0,
+                             stream: int = 0) -> None:
+        """Asynchronous frame_moments into device planes (gi_frame_moments_device), ordered on the device with the
+        scene's renders; pointers are ints, an output of 0 is not written."""
+        f = _aov_frame(w, h, window)
+        m = Moments(d_mean or None, d_var or None, d_samples or None)
+        _check(lib().gi_frame_moments_device(self._h, ctypes.byref(f), ctypes.byref(m), stream or None), "gi_frame_moments_device")
+
     def kat_x_variant(self, flags: int = 0) -> dict:
         """The kernel variant kat_x_query runs with these flags (flags 0: k_seg's for this scene):
         {"LDS", "W4", "SH", "TRI", "CN", "FLAT"} -> bool (gi_kat_x_variant)."""
@@ -823,6 +895,75 @@ def denoise_device(cam: "Camera", w: int, h: int, d_rgb: int, d_t: int, d_normal
     p = _denoise_params(levels, sigma_c, sigma_p, normal_pow_log2, albedo_stop)
     _check(lib().gi_denoise_device(ctypes.byref(cam._c), ctypes.byref(f), ctypes.byref(p), ctypes.byref(io), d_scratch or None,
                                    int(scratch_bytes), stream or None), "gi_denoise_device")
+
+
+def _denoise_var_params(levels, sigma_v, sigma_p, var_floor, normal_pow_log2, albedo_stop) -> DenoiseVarParams:
+    return DenoiseVarParams(int(levels), int(normal_pow_log2), DENOISE_ALBEDO_STOP if albedo_stop else 0, 0, float(sigma_v),
+                            float(sigma_p), float(var_floor))
+
+
+def denoise_var_scratch_bytes(w: int, h: int, window=None, levels: int = 4, sigma_v: float = DENOISE_VAR_SIGMA_V,
+                              sigma_p: float = 0.01, var_floor: float = DENOISE_VAR_FLOOR, normal_pow_log2: int = 5,
+                              albedo_stop: bool = True) -> int:
+    """The bytes of device scratch denoise_var_device needs for this window and these parameters
+    (gi_denoise_var_scratch_bytes; host code, no device)."""
+    f = _aov_frame(w, h, window)
+    p = _denoise_var_params(levels, sigma_v, sigma_p, var_floor, normal_pow_log2, albedo_stop)
+    n = lib().gi_denoise_var_scratch_bytes(ctypes.byref(f), ctypes.byref(p))
+    if n < 0:
+        _check(int(n), "gi_denoise_var_scratch_bytes")
+    return int(n)
+
+
+def denoise_var(cam: "Camera", w: int, h: int, rgb, var, t, normal, albedo=None, window=None, levels: int = 4,
+                sigma_v: float = DENOISE_VAR_SIGMA_V, sigma_p: float = 0.01, var_floor: float = DENOISE_VAR_FLOOR,
+                normal_pow_log2: int = 5, albedo_stop: bool = True, want=DENOISE_VAR_OUTPUTS) -> dict:
+    """The variance-guided filter of gi.h "variance-guided denoiser" from host arrays (gi_denoise_var): denoise's
+    planes plus var (rows, cols, 3), the variance of the mean (DeviceScene.frame_moments' "var", with its "mean" as
+    rgb); the colour stop of a pixel is sigma_v^2 times its prefiltered variance plus var_floor.  Returns the
+    outputs named in want: "rgb" and "var" (rows, cols, 3) float64, "rgb8" (rows, cols, 3) uint8.  ValueError for a
+    wrong shape or want."""
+    want = tuple(want)
+    if not want or any(k not in DENOISE_VAR_OUTPUTS for k in want) or len(set(want)) != len(want):
+        raise ValueError(f"denoise_var: want is a non-empty selection of {DENOISE_VAR_OUTPUTS}")
+    f = _aov_frame(w, h, window)
+    rows, cols = f.y1 - f.y0, f.x1 - f.x0
+    if albedo is None and albedo_stop:
+        raise ValueError("denoise_var: albedo_stop needs the albedo plane")
+
+    def plane(name, a, tail):
+        a = np.ascontiguousarray(a, np.float64)
+        if a.size != rows * cols * (tail[0] if tail else 1):
+            raise ValueError(f"denoise_var: {name} must hold {(rows, cols) + tail} float64")
+        return a
+    ins = {"rgb": plane("rgb", rgb, (3,)), "var": plane("var", var, (3,)), "t": plane("t", t, ()),
+           "normal": plane("normal", normal, (3,))}
+    if albedo is not None:
+        ins["albedo"] = plane("albedo", albedo, (3,))
+    bufs = {"rgb": np.empty((rows, cols, 3), np.float64), "var": np.empty((rows, cols, 3), np.float64),
+            "rgb8": np.empty((rows, cols, 3), np.uint8)}
+    io = DenoiseVarIO(**{k: (a.ctypes.data if a.size else _scratch_ptr()) for k, a in ins.items()},
+                      # (an empty window: valid addresses, the outputs' apart from the inputs')
+                      **{"out_" + k: (bufs[k].ctypes.data if bufs[k].size else _scratch_ptr() + 32) for k in want})
+    p = _denoise_var_params(levels, sigma_v, sigma_p, var_floor, normal_pow_log2, albedo_stop)
+    _check(lib().gi_denoise_var(ctypes.byref(cam._c), ctypes.byref(f), ctypes.byref(p), ctypes.byref(io)), "gi_denoise_var")
+    return {k: bufs[k] for k in want}
+
+
+def denoise_var_device(cam: "Camera", w: int, h: int, d_rgb: int, d_var: int, d_t: int, d_normal: int, d_albedo: int,
+                       d_scratch: int, scratch_bytes: int, d_out_rgb: int = 0, d_out_var: int = 0, d_out_rgb8: int = 0,
+                       window=None, levels: int = 4, sigma_v: float = DENOISE_VAR_SIGMA_V, sigma_p: float = 0.01,
+                       var_floor: float = DENOISE_VAR_FLOOR, normal_pow_log2: int = 5, albedo_stop: bool = True,
+                       stream: int = 0) -> None:
+    """Asynchronous denoise_var of device planes into device outputs on the current device (gi_denoise_var_device);
+    pointers are ints, an output of 0 is not written.  d_scratch: scratch_bytes >= denoise_var_scratch_bytes(...)
+    bytes of device memory, 16-byte aligned, the call's own until its launches have run."""
+    f = _aov_frame(w, h, window)
+    io = DenoiseVarIO(d_rgb or None, d_var or None, d_t or None, d_normal or None, d_albedo or None, d_out_rgb or None,
+                      d_out_var or None, d_out_rgb8 or None)
+    p = _denoise_var_params(levels, sigma_v, sigma_p, var_floor, normal_pow_log2, albedo_stop)
+    _check(lib().gi_denoise_var_device(ctypes.byref(cam._c), ctypes.byref(f), ctypes.byref(p), ctypes.byref(io), d_scratch or None,
+                                       int(scratch_bytes), stream or None), "gi_denoise_var_device")
 
 
 def devices_from_env(default=None):

@@ -51,6 +51,11 @@ struct gi_scene {
     bool launched = false;
     uint64_t prog_key = 0;   // progressive passes: the frame's key and the next pass's sample_begin
     int prog_next = -1;
+    // the retained frame (gi.h "sample moments"): the last render, if it was a whole Mode X frame with spp > 1 on
+    // one shard and was issued successfully -- its size, the samples rendered so far (0: no retained frame), the
+    // rows' stride and its camera (k_x_moments_fill repeats the classify pass's test)
+    int keep_w = 0, keep_h = 0, keep_n = 0, keep_spp = 0;
+    CamDev keep_cam;
     std::mutex mu;     // host-side calls on one scene are serialised
     int device = -1;
     int64_t bytes = 0;
@@ -440,6 +445,15 @@ int prog_check(gi_scene* s, const gi_camera& c, const double light[3], int w, in
 void prog_done(gi_scene* s, const gi_opts& o) {
     s->prog_next = (o.sample_end > 0 && o.sample_end < o.spp) ? o.sample_end : -1;
 }
+// a whole frame has been issued: it is the retained frame if it left per-sample rows of one shard
+void keep_frame(gi_scene* s, const CamDev& cd, int w, int h, const gi_opts& o) {
+    if (o.mode != GI_MODE_X || o.spp < 2 || o.shard_count != 1) return;
+    s->keep_w = w;
+    s->keep_h = h;
+    s->keep_n = o.sample_end > 0 ? o.sample_end : o.spp;
+    s->keep_spp = o.spp;
+    s->keep_cam = cd;
+}
 }  // namespace
 
 int band_rows_of(const gi_opts* o, int h) {
@@ -550,6 +564,7 @@ std::mutex& scene_mutex(gi_scene* s) { return s->mu; }
 // y0 = 0, h = its height) or of one shard of it, into device buffers on `stream`.
 int scene_render_band(gi_scene* s, const CamDev& cd, const double light[3], int w, int h, int y0, const gi_opts& o,
                       double* d_rgb, uint8_t* d_rgb8, hipStream_t stream, bool timer) {
+    s->keep_n = 0;   // (every render ends the retained frame; a whole frame that succeeds becomes the next one)
     int rc = bind_device(s->device);
     if (rc || (rc = ensure_xscratch(s, w, h, &o)) || (timer && (rc = ensure_timer(s, &o)))) return rc;
     return issue_render(s, cd, v3(light[0], light[1], light[2]), w, h, y0, o, d_rgb, d_rgb8, stream, timer);
@@ -644,14 +659,18 @@ int gi_render_device(gi_scene* s, const gi_camera* cam, const double light[3], i
     return guard([&]() -> int {
         DeviceRestore keep;   // the caller's current device, restored on return
         if (!s) return fail(GI_ERR_ARG, "null scene");
+        std::lock_guard<std::mutex> lk(s->mu);
+        s->keep_n = 0;   // (a refused render too ends the retained frame)
         int rc = check_opts(w, h, o);
         if (rc) return rc;
         if (!cam || !light) return fail(GI_ERR_ARG, "null camera or light");
-        std::lock_guard<std::mutex> lk(s->mu);
         if ((rc = prog_check(s, *cam, light, w, h, *o))) return rc;
-        rc = scene_render_band(s, make_cam(*cam, w), light, w, h, 0, *o, d_rgb, d_rgb8, static_cast<hipStream_t>(stream),
-                               true);
-        if (rc == GI_OK) prog_done(s, *o);
+        const CamDev cd = make_cam(*cam, w);
+        rc = scene_render_band(s, cd, light, w, h, 0, *o, d_rgb, d_rgb8, static_cast<hipStream_t>(stream), true);
+        if (rc == GI_OK) {
+            prog_done(s, *o);
+            keep_frame(s, cd, w, h, *o);
+        }
         return rc;
     });
 }
@@ -661,11 +680,12 @@ int gi_render(gi_scene* s, const gi_camera* cam, const double light[3], int w, i
     return guard([&]() -> int {
         DeviceRestore keep;   // the caller's current device, restored on return
         if (!s) return fail(GI_ERR_ARG, "null scene");
+        std::lock_guard<std::mutex> lk(s->mu);
+        s->keep_n = 0;   // (a refused render too ends the retained frame)
         int rc = check_opts(w, h, o);
         if (rc) return rc;
         if (!cam || !light) return fail(GI_ERR_ARG, "null camera or light");
         if (o->shard_count != 1) return fail(GI_ERR_ARG, "gi_render renders whole frames; use gi_render_device or gi_multi to shard");
-        std::lock_guard<std::mutex> lk(s->mu);
         if ((rc = bind_device(s->device))) return rc;
         // progressive bands of whole tile rows (the reference fills rows in order, raytracer.h:32-33,
         // and the Viewer repaints what is done, viewer.h:18-21); cancel is polled between bands.
@@ -723,6 +743,8 @@ int gi_render(gi_scene* s, const gi_camera* cam, const double light[3], int w, i
         const hipError_t e1 = hipStreamSynchronize(hp.render), e2 = hipStreamSynchronize(hp.copy);
         if (rc == GI_OK && (e1 != hipSuccess || e2 != hipSuccess)) rc = hip_fail(e1 != hipSuccess ? e1 : e2, "render");
         if (rc == GI_OK) prog_done(s, *o);
+        if (rc == GI_OK && n_bands == 1) keep_frame(s, cd, w, h, *o);
+        else s->keep_n = 0;
         return rc;
     });
 }
@@ -1032,6 +1054,87 @@ int gi_camera_rays(const gi_camera* cam, const gi_aov_frame* frame, double* rays
     });
 }
 
+// ---- sample moments of the retained frame (gi.h "sample moments"; gi_kernels.hip k_x_moments) ----
+// Unlike the queries above these read the scene's Mode X scratch: under the scene's mutex, and ordered on the
+// device with the scene's `last` event in both directions.  Nothing of the progressive-frame state is touched.
+namespace {
+// everything of a moments call; the scene's mutex is held.  *empty: the window holds no pixel
+int check_moments(const gi_scene* s, const gi_aov_frame* frame, const gi_moments* out, bool* empty) {
+    if (!out->mean && !out->var && !out->samples) return fail(GI_ERR_ARG, "gi_frame_moments: every output is null");
+    if (s->keep_n == 0)
+        return fail(GI_ERR_ARG, "gi_frame_moments: no retained frame (the scene's last render was not a whole Mode X frame with "
+                                "spp > 1 on one shard, or it failed)");
+    if (s->keep_n < 2) return fail(GI_ERR_ARG, "gi_frame_moments: fewer than 2 samples rendered so far");
+    const int rc = check_frame_window(frame, empty);
+    if (rc) return rc;
+    if (frame->w != s->keep_w || frame->h != s->keep_h) return fail(GI_ERR_ARG, "gi_frame_moments: the frame is not the retained frame's size");
+    return GI_OK;
+}
+int issue_moments(gi_scene* s, const gi_aov_frame& f, const gi_moments& d, hipStream_t stream) {
+    int rc = bind_device(s->device);
+    if (rc) return rc;
+    hipError_t e = hipSuccess;
+    if (s->launched && (e = hipStreamWaitEvent(stream, s->last, 0)) != hipSuccess) return hip_fail(e, "hipStreamWaitEvent");
+    const MomentsIO io{f.x0, f.y0, f.x1 - f.x0, f.y1 - f.y0, s->keep_spp, s->keep_n, d.mean, d.var, d.samples};
+    if ((e = launch_moments(s->dev, s->xs, s->keep_cam, f.w, f.h, io, stream)) != hipSuccess) return hip_fail(e, "gi_frame_moments launch");
+    // the scene's next render overwrites the rows: it waits for this call
+    if ((e = hipEventRecord(s->last, stream)) != hipSuccess) return hip_fail(e, "hipEventRecord");
+    return GI_OK;
+}
+}  // namespace
+
+int gi_frame_samples_info(gi_scene* s, int32_t* w, int32_t* h, int32_t* n, int32_t* spp) {
+    return guard([&]() -> int {
+        if (!s) return fail(GI_ERR_ARG, "null scene");
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (s->keep_n == 0) return fail(GI_ERR_ARG, "gi_frame_samples_info: no retained frame");
+        if (w) *w = s->keep_w;
+        if (h) *h = s->keep_h;
+        if (n) *n = s->keep_n;
+        if (spp) *spp = s->keep_spp;
+        return GI_OK;
+    });
+}
+
+int gi_frame_moments_device(gi_scene* s, const gi_aov_frame* frame, const gi_moments* d_out, void* stream) {
+    return guard([&]() -> int {
+        DeviceRestore keep;   // the caller's current device, restored on return
+        if (!s) return fail(GI_ERR_ARG, "null scene");
+        if (!frame || !d_out) return fail(GI_ERR_ARG, "null frame or output struct");
+        std::lock_guard<std::mutex> lk(s->mu);
+        bool empty = false;
+        const int rc = check_moments(s, frame, d_out, &empty);
+        if (rc || empty) return rc;
+        return issue_moments(s, *frame, *d_out, static_cast<hipStream_t>(stream));
+    });
+}
+
+int gi_frame_moments(gi_scene* s, const gi_aov_frame* frame, const gi_moments* out) {
+    return guard([&]() -> int {
+        DeviceRestore keep;   // the caller's current device, restored on return
+        if (!s) return fail(GI_ERR_ARG, "null scene");
+        if (!frame || !out) return fail(GI_ERR_ARG, "null frame or output struct");
+        std::lock_guard<std::mutex> lk(s->mu);
+        bool empty = false;
+        int rc = check_moments(s, frame, out, &empty);
+        if (rc || empty) return rc;
+        if ((rc = bind_device(s->device))) return rc;
+        const size_t m = (size_t)(frame->x1 - frame->x0) * (size_t)(frame->y1 - frame->y0), ns = m * 3 * (size_t)s->keep_n;
+        DevBuf dm, dv, ds;
+        hipError_t e = hipSuccess;
+        if (out->mean) e = dm.alloc(m * 3 * sizeof(double));
+        if (e == hipSuccess && out->var) e = dv.alloc(m * 3 * sizeof(double));
+        if (e == hipSuccess && out->samples) e = ds.alloc(ns * sizeof(double));
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc (moments staging)");
+        const gi_moments d{static_cast<double*>(dm.p), static_cast<double*>(dv.p), static_cast<double*>(ds.p)};
+        if ((rc = issue_moments(s, *frame, d, nullptr))) return rc;
+        if (out->mean) e = hipMemcpy(out->mean, dm.p, m * 3 * sizeof(double), hipMemcpyDeviceToHost);   // (synchronous copies on the launch's stream)
+        if (e == hipSuccess && out->var) e = hipMemcpy(out->var, dv.p, m * 3 * sizeof(double), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && out->samples) e = hipMemcpy(out->samples, ds.p, ns * sizeof(double), hipMemcpyDeviceToHost);
+        return e == hipSuccess ? GI_OK : hip_fail(e, "gi_frame_moments");
+    });
+}
+
 // ---- denoiser (gi.h "denoiser"; gi_denoise.hip k_dn_prep, k_dn_level) ----
 // No scene and no state: the caller's planes and scratch on the current device.
 namespace {
@@ -1114,6 +1217,96 @@ int gi_denoise(const gi_camera* cam, const gi_aov_frame* frame, const gi_denoise
         if (io->out_rgb) e = hipMemcpy(io->out_rgb, dout.p, m * 3 * sizeof(double), hipMemcpyDeviceToHost);   // (synchronous copies on the launch's stream)
         if (e == hipSuccess && io->out_rgb8) e = hipMemcpy(io->out_rgb8, dout8.p, m * 3, hipMemcpyDeviceToHost);
         return e == hipSuccess ? GI_OK : hip_fail(e, "gi_denoise");
+    });
+}
+
+// ---- variance-guided denoiser (gi.h "variance-guided denoiser"; gi_denoise.hip k_dnv_g, k_dnv_level) ----
+namespace {
+int check_denoise_var_params(const gi_denoise_var_params* p) {
+    if (!p) return fail(GI_ERR_ARG, "null denoise parameters");
+    const gi_denoise_params q{p->levels, p->normal_pow_log2, p->flags, p->reserved, p->sigma_v, p->sigma_p};
+    const int rc = check_denoise_params(&q);   // (sigma_v judged as sigma_c)
+    if (rc) return rc;
+    if (!(p->var_floor > 0) || !std::isfinite(p->var_floor)) return fail(GI_ERR_ARG, "gi_denoise_var: var_floor must be finite and > 0");
+    return GI_OK;
+}
+int check_denoise_var(const gi_camera* cam, const gi_aov_frame* frame, const gi_denoise_var_params* p, const gi_denoise_var_io* io,
+                      bool* empty) {
+    if (!io) return fail(GI_ERR_ARG, "null denoise io");
+    int rc = check_aov_frame(cam, frame, empty);
+    if (rc || (rc = check_denoise_var_params(p))) return rc;
+    if (!io->rgb || !io->var || !io->t || !io->normal) return fail(GI_ERR_ARG, "gi_denoise_var: null rgb, var, t or normal");
+    if (!io->out_rgb && !io->out_var && !io->out_rgb8) return fail(GI_ERR_ARG, "gi_denoise_var: every output is null");
+    if ((p->flags & GI_DENOISE_ALBEDO_STOP) && !io->albedo) return fail(GI_ERR_ARG, "gi_denoise_var: the albedo stop needs the albedo plane");
+    if (io->out_rgb == io->rgb || io->out_var == io->var) return fail(GI_ERR_ARG, "gi_denoise_var: out_rgb must not be rgb, out_var not var");
+    return GI_OK;
+}
+int64_t denoise_var_bytes(const gi_aov_frame& f, const gi_denoise_var_params& p) {
+    return dnv_scratch_bytes((long long)(f.x1 - f.x0) * (long long)(f.y1 - f.y0), p.levels, (p.flags & GI_DENOISE_ALBEDO_STOP) != 0);
+}
+DnvIO dnv_io(const gi_aov_frame& f, const gi_denoise_var_io& d) {
+    return DnvIO{f.x0, f.y0, f.x1 - f.x0, f.y1 - f.y0, d.rgb, d.var, d.t, d.normal, d.albedo, d.out_rgb, d.out_var, d.out_rgb8};
+}
+}  // namespace
+
+int64_t gi_denoise_var_scratch_bytes(const gi_aov_frame* frame, const gi_denoise_var_params* p) {   // (nothing here can throw)
+    if (!frame) return fail(GI_ERR_ARG, "null frame");
+    bool empty = false;
+    int rc = check_frame_window(frame, &empty);
+    if (rc || (rc = check_denoise_var_params(p))) return rc;
+    return empty ? 0 : denoise_var_bytes(*frame, *p);
+}
+
+int gi_denoise_var_device(const gi_camera* cam, const gi_aov_frame* frame, const gi_denoise_var_params* p, const gi_denoise_var_io* d_io,
+                          void* d_scratch, int64_t scratch_bytes, void* stream) {
+    return guard([&]() -> int {
+        bool empty = false;
+        const int rc = check_denoise_var(cam, frame, p, d_io, &empty);
+        if (rc) return rc;
+        if (scratch_bytes < (empty ? 0 : denoise_var_bytes(*frame, *p)))
+            return fail(GI_ERR_ARG, "gi_denoise_var: scratch_bytes below gi_denoise_var_scratch_bytes");
+        if (empty) return GI_OK;
+        if (!d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 15))
+            return fail(GI_ERR_ARG, "gi_denoise_var: the device scratch must be non-null and 16-byte aligned");
+        const hipError_t e = launch_denoise_var(make_cam(*cam, frame->w), dnv_io(*frame, *d_io), *p, d_scratch, static_cast<hipStream_t>(stream));
+        return e == hipSuccess ? GI_OK : hip_fail(e, "gi_denoise_var launch");
+    });
+}
+
+int gi_denoise_var(const gi_camera* cam, const gi_aov_frame* frame, const gi_denoise_var_params* p, const gi_denoise_var_io* io) {
+    return guard([&]() -> int {
+        bool empty = false;
+        const int rc = check_denoise_var(cam, frame, p, io, &empty);
+        if (rc) return rc;
+        if (empty) return GI_OK;
+        const size_t m = (size_t)(frame->x1 - frame->x0) * (size_t)(frame->y1 - frame->y0), b3 = m * 3 * sizeof(double);
+        const bool stop = (p->flags & GI_DENOISE_ALBEDO_STOP) != 0;
+        DevBuf drgb, dvar, dt, dn, da, dout, dovar, dout8, dscr;
+        hipError_t e = drgb.alloc(b3);
+        if (e == hipSuccess) e = dvar.alloc(b3);
+        if (e == hipSuccess) e = dt.alloc(m * sizeof(double));
+        if (e == hipSuccess) e = dn.alloc(b3);
+        if (e == hipSuccess && stop) e = da.alloc(b3);
+        if (e == hipSuccess && io->out_rgb) e = dout.alloc(b3);
+        if (e == hipSuccess && io->out_var) e = dovar.alloc(b3);
+        if (e == hipSuccess && io->out_rgb8) e = dout8.alloc(m * 3);
+        if (e == hipSuccess) e = dscr.alloc((size_t)denoise_var_bytes(*frame, *p));
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc (denoiser staging)");
+        e = hipMemcpy(drgb.p, io->rgb, b3, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(dvar.p, io->var, b3, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(dt.p, io->t, m * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(dn.p, io->normal, b3, hipMemcpyHostToDevice);
+        if (e == hipSuccess && stop) e = hipMemcpy(da.p, io->albedo, b3, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return hip_fail(e, "gi_denoise_var");
+        const gi_denoise_var_io d{static_cast<const double*>(drgb.p), static_cast<const double*>(dvar.p), static_cast<const double*>(dt.p),
+                                  static_cast<const double*>(dn.p), static_cast<const double*>(da.p), static_cast<double*>(dout.p),
+                                  static_cast<double*>(dovar.p), static_cast<uint8_t*>(dout8.p)};
+        e = launch_denoise_var(make_cam(*cam, frame->w), dnv_io(*frame, d), *p, dscr.p, nullptr);
+        if (e != hipSuccess) return hip_fail(e, "gi_denoise_var launch");
+        if (io->out_rgb) e = hipMemcpy(io->out_rgb, dout.p, b3, hipMemcpyDeviceToHost);   // (synchronous copies on the launch's stream)
+        if (e == hipSuccess && io->out_var) e = hipMemcpy(io->out_var, dovar.p, b3, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && io->out_rgb8) e = hipMemcpy(io->out_rgb8, dout8.p, m * 3, hipMemcpyDeviceToHost);
+        return e == hipSuccess ? GI_OK : hip_fail(e, "gi_denoise_var");
     });
 }
 

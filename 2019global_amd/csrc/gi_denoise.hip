@@ -9,7 +9,10 @@
 //                the outputs
 //   k_dn_level_lds  the same level for steps 1 and 2 with the tile and its halo staged in LDS once: it won the
 //                A/B against the direct form there (DESIGN.md §9 "Denoiser"; profiles/denoise_ab.txt)
-// Lane mapping of all three: workgroup tiles of 64 x 4 window pixels, a wave per tile row, lanes along x -- every
+//   k_dnv_g, k_dnv_level  the variance-guided filter (gi.h "variance-guided denoiser"): per level the 3 x 3 prefilter
+//                of the variance plane, then k_dn_level's direct-gather level with the colour stop per pixel and
+//                the variance carried along
+// Lane mapping of all of them: workgroup tiles of 64 x 4 window pixels, a wave per tile row, lanes along x -- every
 // tap of a wave is one contiguous run of records, and the four rows of a tile share their vertical taps; the direct
 // levels' tiles are dealt to the XCDs in bands (dn_tile_of).
 // 64-bit indices.  Resources and rates: DESIGN.md §9 "Denoiser".
@@ -139,7 +142,7 @@ __device__ __forceinline__ double dn_h(int k) { return k == 2 ? 0.375 : ((k == 1
 struct DnAcc {
     double w, r, g, b;
 };
-__device__ __forceinline__ void dn_tap(DnAcc& a, double k, V3 np, V3 Pp, double sp, V3 cp, V3 nq, V3 Pq, V3 cq, int npow, double sigma2) {
+__device__ __forceinline__ double dn_weight(double k, V3 np, V3 Pp, double sp, V3 cp, V3 nq, V3 Pq, V3 cq, int npow, double sigma2) {
     double wn = dot(np, nq);
     wn = wn > 0.0 ? wn : 0.0;
     for (int s = 0; s < npow; ++s) wn = wn * wn;
@@ -148,7 +151,10 @@ __device__ __forceinline__ void dn_tap(DnAcc& a, double k, V3 np, V3 Pp, double 
     wp = wp > 0.0 ? wp : 0.0;
     const V3 e = cp - cq;
     const double wc = 1.0 / (1.0 + dot(e, e) / sigma2);
-    const double wt = ((k * wn) * wp) * wc;
+    return ((k * wn) * wp) * wc;
+}
+__device__ __forceinline__ void dn_tap(DnAcc& a, double k, V3 np, V3 Pp, double sp, V3 cp, V3 nq, V3 Pq, V3 cq, int npow, double sigma2) {
+    const double wt = dn_weight(k, np, Pp, sp, cp, nq, Pq, cq, npow, sigma2);
     a.w += wt;
     a.r += wt * cq.x;
     a.g += wt * cq.y;
@@ -343,10 +349,182 @@ hipError_t dn_level(dim3 grid, dim3 block, hipStream_t stream, const DnIO& io, i
     return hipGetLastError();
 }
 
+// ---- the variance-guided filter (gi.h "variance-guided denoiser"; gi_denoise_var*) ----
+// The same taps and stops, with the level's colour stop per pixel from the variance of the mean: k_dnv_g writes the
+// 3 x 3 prefiltered variance g of the level's variance plane, k_dnv_level reads g at the centre, forms sigma2_p and
+// carries the variance through the level beside the colour (three more doubles per tap).  Every level gathers from
+// global memory (k_dn_level's form and tile deal); the LDS-staged form is not built for it: DESIGN.md §9.
+
+// g_p of a valid pixel: the G x G weighted mean of v = (V.r + V.g) + V.b over its valid 3 x 3 neighbours in the window
+__global__ __launch_bounds__(kDnTileW * kDnTileH) void k_dnv_g(int cols, int rows, const DnGuide* __restrict__ guide,
+                                                                const double* __restrict__ vin, double* __restrict__ g) {
+    const DnTiles tl = dn_tiles(cols, rows);
+    for (long long slot = blockIdx.x; slot < tl.n_tiles; slot += gridDim.x) {
+        int px = 0, py = 0;
+        if (!dn_pixel(tl, slot, cols, rows, px, py)) continue;
+        const long long i = (long long)py * (long long)cols + (long long)px;
+        const double2 gp3 = reinterpret_cast<const double2*>(guide + i)[3];
+        double out = 0.0;
+        if (gp3.y != 0.0) {
+            double sum_k = 0.0, sum_v = 0.0;
+#pragma unroll
+            for (int dy = -1; dy <= 1; ++dy) {
+#pragma unroll
+                for (int dx = -1; dx <= 1; ++dx) {
+                    const int qy = py + dy, qx = px + dx;
+                    const bool in = qy >= 0 && qy < rows && qx >= 0 && qx < cols;
+                    const long long j = in ? (long long)qy * (long long)cols + (long long)qx : i;
+                    const double2 gq3 = reinterpret_cast<const double2*>(guide + j)[3];
+                    const double v = (vin[3 * j] + vin[3 * j + 1]) + vin[3 * j + 2];
+                    if (!in || gq3.y == 0.0) continue;
+                    const double k = (dx == 0 ? 0.5 : 0.25) * (dy == 0 ? 0.5 : 0.25);
+                    sum_k += k;
+                    sum_v += k * v;
+                }
+            }
+            out = sum_v / sum_k;
+        }
+        g[i] = out;
+    }
+}
+
+struct DnvAcc {
+    double w, r, g, b, vr, vg, vb;
+};
+
+// One level: c_out, v_out = the filtered c_in and the propagated v_in at step `step`; sv2 = sigma_v sigma_v
+// (+inf: no colour stop, whatever g is).  LAST: min(c, 1) into cout / out8 and the variance, as it is, into vout
+// (each may be null).  Invalid pixels copy both through.
+template <bool STOP, bool LAST>
+__global__ __launch_bounds__(kDnTileW * kDnTileH) void k_dnv_level(int cols, int rows, int step, int npow, double sv2, double var_floor,
+                                                                    const DnGuide* __restrict__ guide,
+                                                                    const DnAlbedo* __restrict__ albedo, const double* __restrict__ gpl,
+                                                                    const double* __restrict__ cin, const double* __restrict__ vin,
+                                                                    double* __restrict__ cout, double* __restrict__ vout,
+                                                                    uint8_t* __restrict__ out8) {
+    const DnTiles tl = dn_tiles(cols, rows);
+    for (long long slot = blockIdx.x; slot < tl.n_tiles; slot += gridDim.x) {
+        const long long tile = dn_tile_of(slot, tl);
+        int px = 0, py = 0;
+        if (!dn_pixel(tl, tile, cols, rows, px, py)) continue;
+        const long long i = (long long)py * (long long)cols + (long long)px;
+        const DnGuide gp = dn_load_guide(guide, i);
+        const double cr = cin[3 * i], cg = cin[3 * i + 1], cb = cin[3 * i + 2];
+        double r = cr, g = cg, b = cb;
+        double vr = vin[3 * i], vg = vin[3 * i + 1], vb = vin[3 * i + 2];
+        if (gp.valid != 0.0) {
+            double ar = 0.0, ag = 0.0, ab = 0.0;
+            if (STOP) {
+                const double2* qa = reinterpret_cast<const double2*>(albedo + i);
+                const double2 a0 = qa[0], a1 = qa[1];
+                ar = a0.x; ag = a0.y; ab = a1.x;
+            }
+            const double sigma2 = sv2 < INFINITY ? sv2 * gpl[i] + var_floor : INFINITY;
+            const V3 np = v3(gp.n[0], gp.n[1], gp.n[2]);
+            const V3 Pp = v3(gp.P[0], gp.P[1], gp.P[2]);
+            DnvAcc acc = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int dy = -2; dy <= 2; ++dy) {
+#pragma unroll
+                for (int dx = -2; dx <= 2; ++dx) {
+                    // (every tap's loads are issued whether it counts or not: k_dn_level)
+                    const long long qy = (long long)py + (long long)step * dy, qx = (long long)px + (long long)step * dx;
+                    const bool in = qy >= 0 && qy < rows && qx >= 0 && qx < cols;
+                    const long long j = in ? qy * (long long)cols + qx : i;
+                    const DnGuide gq = dn_load_guide(guide, j);
+                    bool use = in && gq.valid != 0.0;
+                    if (STOP) {
+                        const double2* qa = reinterpret_cast<const double2*>(albedo + j);
+                        const double2 a0 = qa[0], a1 = qa[1];
+                        use = use && a0.x == ar && a0.y == ag && a1.x == ab;
+                    }
+                    const double qr = cin[3 * j], qg = cin[3 * j + 1], qb = cin[3 * j + 2];
+                    const double ur = vin[3 * j], ug = vin[3 * j + 1], ub = vin[3 * j + 2];
+                    if (!use) continue;
+                    const double wt = dn_weight(dn_h(dx + 2) * dn_h(dy + 2), np, Pp, gp.sp, v3(cr, cg, cb), v3(gq.n[0], gq.n[1], gq.n[2]),
+                                                v3(gq.P[0], gq.P[1], gq.P[2]), v3(qr, qg, qb), npow, sigma2);
+                    const double w2 = wt * wt;
+                    acc.w += wt;
+                    acc.r += wt * qr;
+                    acc.g += wt * qg;
+                    acc.b += wt * qb;
+                    acc.vr += w2 * ur;
+                    acc.vg += w2 * ug;
+                    acc.vb += w2 * ub;
+                }
+            }
+            const double ww = acc.w * acc.w;
+            r = acc.r / acc.w;
+            g = acc.g / acc.w;
+            b = acc.b / acc.w;
+            vr = acc.vr / ww;
+            vg = acc.vg / ww;
+            vb = acc.vb / ww;
+        }
+        dn_store<LAST>(i, r, g, b, cout, out8);
+        if (vout) {
+            vout[3 * i] = vr;
+            vout[3 * i + 1] = vg;
+            vout[3 * i + 2] = vb;
+        }
+    }
+}
+
 long long dn_round16(long long b) { return (b + 15) & ~15ll; }
 int dn_planes(int levels) { return levels - 1 < 2 ? levels - 1 : 2; }
 
 }  // namespace
+
+// gi_denoise_var's scratch: gi_denoise's for the same window and levels, then as many variance planes as colour
+// planes, then the g plane.
+long long dnv_scratch_bytes(long long n_px, int levels, bool albedo_stop) {
+    return dn_scratch_bytes(n_px, levels, albedo_stop) + (long long)dn_planes(levels) * dn_round16(n_px * 3 * (long long)sizeof(double)) +
+           dn_round16(n_px * (long long)sizeof(double));
+}
+
+// gi_denoise_var_device's launches on `stream`: k_dn_prep, then per level k_dnv_g and k_dnv_level.
+hipError_t launch_denoise_var(const CamDev& cam, const DnvIO& io, const gi_denoise_var_params& p, void* scratch, hipStream_t stream) {
+    const long long n_px = (long long)io.cols * (long long)io.rows;
+    const bool stop = (p.flags & GI_DENOISE_ALBEDO_STOP) != 0;
+    const long long plane_b = dn_round16(n_px * 3 * (long long)sizeof(double));
+    char* base = static_cast<char*>(scratch);
+    DnGuide* guide = reinterpret_cast<DnGuide*>(base);
+    base += dn_round16(n_px * (long long)sizeof(DnGuide));
+    DnAlbedo* albedo = nullptr;
+    if (stop) {
+        albedo = reinterpret_cast<DnAlbedo*>(base);
+        base += dn_round16(n_px * (long long)sizeof(DnAlbedo));
+    }
+    const int np = dn_planes(p.levels);
+    double* cpl[2] = {reinterpret_cast<double*>(base), reinterpret_cast<double*>(base + plane_b)};
+    base += np * plane_b;
+    double* vpl[2] = {reinterpret_cast<double*>(base), reinterpret_cast<double*>(base + plane_b)};
+    base += np * plane_b;
+    double* g = reinterpret_cast<double*>(base);
+    const DnTiles tl = dn_tiles(io.cols, io.rows);
+    const dim3 grid((unsigned)(tl.n_tiles < kDnMaxGrid ? tl.n_tiles : kDnMaxGrid)), block(kDnTileW, kDnTileH);
+    hipLaunchKernelGGL(k_dn_prep, grid, block, 0, stream, cam, io.x0, io.y0, io.cols, io.rows, p.sigma_p, io.t, io.nrm,
+                       stop ? io.alb : nullptr, guide, albedo);
+    hipError_t e = hipGetLastError();
+    const double sv2 = p.sigma_v * p.sigma_v;
+    const double* cin = io.rgb;
+    const double* vin = io.var;
+    for (int i = 0; i < p.levels && e == hipSuccess; ++i) {
+        const bool last = i == p.levels - 1;
+        double* cout = last ? io.out : cpl[i & 1];
+        double* vout = last ? io.out_var : vpl[i & 1];
+        uint8_t* o8 = last ? io.out8 : nullptr;
+        if (sv2 < INFINITY) hipLaunchKernelGGL(k_dnv_g, grid, block, 0, stream, io.cols, io.rows, guide, vin, g);
+        with_bools([&](auto S, auto L) {
+            hipLaunchKernelGGL((k_dnv_level<S.value, L.value>), grid, block, 0, stream, io.cols, io.rows, 1 << i, p.normal_pow_log2, sv2,
+                               p.var_floor, guide, albedo, g, cin, vin, cout, vout, o8);
+        }, stop, last);
+        e = hipGetLastError();
+        cin = cout;
+        vin = vout;
+    }
+    return e;
+}
 
 // The scratch of one call over n_px window pixels: the guide records, the albedo records (albedo stop), and
 // the colour planes between levels (none for one level, one for two, else two), each section 16-byte aligned.

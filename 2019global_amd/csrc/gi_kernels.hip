@@ -884,6 +884,178 @@ __global__ __launch_bounds__(256) void k_x_reduce(TileMap m, XWork wk, int spp, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// Sample moments of the retained frame (gi.h "sample moments"; gi_frame_moments*): the per-sample radiance rows
+// k_x_reduce sums, read again -- per listed pixel inside the window the mean of its first n rows (k_x_reduce's
+// sum over n), the sample variance of that mean by a second pass over the rows (d = x - mean; m2 += d d, one
+// multiply then one add), and the rows themselves.  Outputs are row-major over the window.  The pixels the
+// classify pass did not list have no row: k_x_moments_fill writes their +0 (the same frustum test decides it, so
+// the two kernels write disjoint pixels and together every pixel of the window).
+// GI_MOMENTS_LDS: 1 the wave-cooperative form (a wave of 64 listed pixels loads their rows coalesced, a chunk of
+// samples at a time, into padded LDS and every lane sums its own pixel from there); 0 one lane per listed pixel
+// straight from global memory, k_x_reduce's access pattern (64 separate lines per load instruction).  Same sums in
+// the same order.  A/B builds: build.py --variant NAME GI_MOMENTS_LDS=0|1 (DESIGN.md §9 "Sample moments").
+// ---------------------------------------------------------------------------------------------
+#ifndef GI_MOMENTS_LDS
+#define GI_MOMENTS_LDS 0   // (the plain form won the A/B on the device)
+#endif
+struct XMoments {
+    const unsigned* list;    // the retained frame's work list and its count (k_x_classify's)
+    const unsigned* n_list;
+    const double* part;      // its rows [list index][sample][3], row stride spp samples
+    int spp, n;              // the frame's spp; the samples rendered so far (2 <= n <= spp)
+    int x0, y0, cols, rows;  // the window
+    double *mean, *var, *samples;   // each may be null
+};
+
+// the window index of listed pixel i, -1 outside the window
+__device__ __forceinline__ long long moments_pixel(const TileMap& m, const XMoments& a, unsigned i) {
+    const unsigned ps = a.list[i];
+    long long idx = -1;
+    int x = 0, y = 0;
+    slot_pixel(m, (long long)(ps >> 6), (int)(ps & 63), idx, x, y);
+    x -= a.x0;
+    y -= a.y0;
+    return (x >= 0 && x < a.cols && y >= 0 && y < a.rows) ? (long long)y * (long long)a.cols + (long long)x : -1;
+}
+__device__ __forceinline__ void moments_store(const XMoments& a, long long o, double sa, double sb, double sc, double va, double vb,
+                                              double vc, bool second) {
+    const double n = (double)a.n;
+    if (!second) {
+        if (a.mean) { a.mean[3 * o] = sa; a.mean[3 * o + 1] = sb; a.mean[3 * o + 2] = sc; }
+    } else if (a.var) {
+        const double n1 = (double)(a.n - 1);
+        a.var[3 * o] = (va / n1) / n;
+        a.var[3 * o + 1] = (vb / n1) / n;
+        a.var[3 * o + 2] = (vc / n1) / n;
+    }
+}
+
+#if !GI_MOMENTS_LDS
+__global__ __launch_bounds__(256) void k_x_moments(TileMap m, XMoments a) {
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= *a.n_list) return;
+    const long long o = moments_pixel(m, a, i);
+    if (o < 0) return;
+    const double* p = a.part + 3 * (size_t)i * (size_t)a.spp;
+    // even spp: the row is 16-byte aligned and two samples come in three 16-byte loads, as in k_x_reduce (half the
+    // load instructions); the sums take the samples in the same order
+    const double2* q = reinterpret_cast<const double2*>(p);
+    const bool pairs = (a.spp & 1) == 0;
+    double sa = 0, sb = 0, sc = 0;
+    int s = 0;
+    if (pairs) {
+        for (; s + 1 < a.n; s += 2) {
+            const double2 v0 = q[3 * (s >> 1)], v1 = q[3 * (s >> 1) + 1], v2 = q[3 * (s >> 1) + 2];
+            sa = sa + v0.x;
+            sb = sb + v0.y;
+            sc = sc + v1.x;
+            sa = sa + v1.y;
+            sb = sb + v2.x;
+            sc = sc + v2.y;
+        }
+    }
+    for (; s < a.n; ++s) {
+        sa = sa + p[3 * s];
+        sb = sb + p[3 * s + 1];
+        sc = sc + p[3 * s + 2];
+    }
+    const double n = (double)a.n;
+    const double ma = sa / n, mb = sb / n, mc = sc / n;
+    moments_store(a, o, ma, mb, mc, 0, 0, 0, false);
+    if (!a.var && !a.samples) return;
+    double* out = a.samples ? a.samples + 3 * (size_t)o * (size_t)a.n : nullptr;
+    double va = 0, vb = 0, vc = 0;
+    const auto take = [&](int k, double x0, double x1, double x2) {
+        const double da = x0 - ma, db = x1 - mb, dc = x2 - mc;
+        va = va + da * da;
+        vb = vb + db * db;
+        vc = vc + dc * dc;
+        if (out) { out[3 * k] = x0; out[3 * k + 1] = x1; out[3 * k + 2] = x2; }
+    };
+    s = 0;
+    if (pairs) {
+        for (; s + 1 < a.n; s += 2) {
+            const double2 v0 = q[3 * (s >> 1)], v1 = q[3 * (s >> 1) + 1], v2 = q[3 * (s >> 1) + 2];
+            take(s, v0.x, v0.y, v1.x);
+            take(s + 1, v1.y, v2.x, v2.y);
+        }
+    }
+    for (; s < a.n; ++s) take(s, p[3 * s], p[3 * s + 1], p[3 * s + 2]);
+    moments_store(a, o, 0, 0, 0, va, vb, vc, true);
+}
+#else
+// A workgroup is one wave and takes listed pixels [64 b, 64 b + 64).  Their rows lie one behind the other in
+// `part`, so a chunk of kMomChunk samples of all 64 is 64 runs of 3 kMomChunk doubles: consecutive lanes load
+// consecutive doubles of a run.  In LDS a pixel's chunk takes kMomRow = 3 kMomChunk + 1 doubles: the odd stride
+// puts the lanes' rows on different banks when each reads its own row at the same offset.
+constexpr int kMomChunk = 8, kMomRow = 3 * kMomChunk + 1;
+__global__ __launch_bounds__(64) void k_x_moments(TileMap m, XMoments a) {
+    __shared__ double s_row[64 * kMomRow];
+    const unsigned n_list = *a.n_list, base = blockIdx.x * 64u;
+    if (base >= n_list) return;
+    const unsigned cnt = n_list - base < 64u ? n_list - base : 64u;
+    const unsigned lane = threadIdx.x;
+    const long long o = lane < cnt ? moments_pixel(m, a, base + lane) : -1;
+    if (!__syncthreads_or(o >= 0)) return;   // none of the wave's pixels is in the window
+    const double* rows = a.part + 3 * (size_t)base * (size_t)a.spp;
+    const double* mine = s_row + lane * kMomRow;
+    const double n = (double)a.n;
+    double sa = 0, sb = 0, sc = 0, ma = 0, mb = 0, mc = 0;
+    double* out = (a.samples && o >= 0) ? a.samples + 3 * (size_t)o * (size_t)a.n : nullptr;
+    for (int pass = 0; pass < 2; ++pass) {   // 0: the sums of the mean; 1: of the variance, and the rows' copy
+        if (pass == 1 && !a.var && !a.samples) break;
+        for (int s0 = 0; s0 < a.n; s0 += kMomChunk) {
+            const unsigned cn = (unsigned)(a.n - s0 < kMomChunk ? a.n - s0 : kMomChunk), per = 3u * cn, total = cnt * per;
+            for (unsigned e = lane; e < total; e += 64u) {
+                const unsigned px = e / per, k = e - px * per;
+                s_row[px * kMomRow + k] = rows[3 * ((size_t)px * (size_t)a.spp + (size_t)s0) + k];
+            }
+            __syncthreads();
+            if (o >= 0) {
+                for (unsigned k = 0; k < cn; ++k) {
+                    const double x0 = mine[3 * k], x1 = mine[3 * k + 1], x2 = mine[3 * k + 2];
+                    if (pass == 0) {
+                        sa = sa + x0;
+                        sb = sb + x1;
+                        sc = sc + x2;
+                    } else {
+                        const double da = x0 - ma, db = x1 - mb, dc = x2 - mc;
+                        sa = sa + da * da;
+                        sb = sb + db * db;
+                        sc = sc + dc * dc;
+                        if (out) { out[3 * (s0 + k)] = x0; out[3 * (s0 + k) + 1] = x1; out[3 * (s0 + k) + 2] = x2; }
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        if (pass == 0) {
+            ma = sa / n; mb = sb / n; mc = sc / n;
+            if (o >= 0) moments_store(a, o, ma, mb, mc, 0, 0, 0, false);
+            sa = sb = sc = 0;
+        } else if (o >= 0) {
+            moments_store(a, o, 0, 0, 0, sa, sb, sc, true);
+        }
+    }
+}
+#endif
+
+// the window's pixels without a row: +0 in every output
+__global__ __launch_bounds__(256) void k_x_moments_fill(DevScene sc, CamDev cam, XMoments a) {
+    const long long n_px = (long long)a.cols * (long long)a.rows;
+    for (long long o = (long long)blockIdx.x * blockDim.x + threadIdx.x; o < n_px; o += (long long)gridDim.x * blockDim.x) {
+        const int y = (int)(o / a.cols), x = (int)(o - (long long)y * a.cols);
+        if (!pixel_misses_box(cam, x + a.x0, y + a.y0, sc.root_lo, sc.root_hi)) continue;
+        if (a.mean) { a.mean[3 * o] = 0; a.mean[3 * o + 1] = 0; a.mean[3 * o + 2] = 0; }
+        if (a.var) { a.var[3 * o] = 0; a.var[3 * o + 1] = 0; a.var[3 * o + 2] = 0; }
+        if (a.samples) {
+            double* out = a.samples + 3 * (size_t)o * (size_t)a.n;
+            for (int k = 0; k < 3 * a.n; ++k) out[k] = 0;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // unshard: packed per-rank tiles -> row-major frame
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_unshard(TileMap m, const double* packed, const uint8_t* packed8, double* rgb,
@@ -1079,6 +1251,22 @@ hipError_t launch_unshard(int w, int h, int shard_count, const double* packed, c
     const TileMap m = make_map(w, h, shard_count, 0);
     const long long n = m.n_tiles * kTile * kTile;
     hipLaunchKernelGGL(k_unshard, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, m, packed, packed8, rgb, rgb8);
+    return hipGetLastError();
+}
+
+// gi_frame_moments_device's launches on `stream`: the fill of the window's unlisted pixels, then k_x_moments over
+// the slots of the whole w x h frame (the work list's length is on the device; slots past it return at once).
+hipError_t launch_moments(const DevScene& sc, const XScratch& xs, const CamDev& cam, int w, int h, const MomentsIO& io,
+                          hipStream_t stream) {
+    const TileMap m = make_map(w, h, 1, 0);
+    const long long n_slots = m.n_local * (kTile * kTile);
+    if (!xs.list || !xs.part || xs.cap < n_slots || xs.spp < io.spp || io.n < 2 || io.n > io.spp) return hipErrorInvalidValue;
+    const XMoments a{xs.list, sc.work + 1, xs.part, io.spp, io.n, io.x0, io.y0, io.cols, io.rows, io.mean, io.var, io.samples};
+    const long long n_px = (long long)io.cols * (long long)io.rows;
+    const long long fgrid = std::min<long long>((n_px + 255) / 256, 1ll << 20);
+    hipLaunchKernelGGL(k_x_moments_fill, dim3((unsigned)fgrid), dim3(256), 0, stream, sc, cam, a);
+    const int block = GI_MOMENTS_LDS ? 64 : 256;
+    hipLaunchKernelGGL(k_x_moments, dim3((unsigned)((n_slots + block - 1) / block)), dim3(block), 0, stream, m, a);
     return hipGetLastError();
 }
 

@@ -39,7 +39,7 @@ struct XKernelCfg {
     int resident;
 };
 
-// ---- gi_kernels.hip: k_mode_x with its classify and reduce passes, k_unshard ----
+// ---- gi_kernels.hip: k_mode_x with its classify and reduce passes, k_x_moments, k_unshard ----
 long long shard_tiles(int w, int h, int shard_count);
 constexpr long long kXWfChunk = 8ll << 20;   // wavefront form: units (pixel samples) per chunk = queue capacity
 hipError_t x_launch_config(const DevScene& sc, int device, XLaunchCfg& cfg);
@@ -49,6 +49,17 @@ hipError_t launch_render(const DevScene& sc, const XLaunchCfg& xc, const CamDev&
                          hipStream_t stream);
 hipError_t launch_unshard(int w, int h, int shard_count, const double* packed, const uint8_t* packed8, double* rgb,
                           uint8_t* rgb8, hipStream_t stream);
+
+// One call of the sample moments (gi_frame_moments*; k_x_moments, k_x_moments_fill): the window [x0, x0 + cols) x
+// [y0, y0 + rows) of the retained frame, its spp (the rows' stride) and the n samples rendered so far, and the
+// output planes, device pointers, row-major over the window; a null output is not written.
+struct MomentsIO {
+    int x0, y0, cols, rows;
+    int spp, n;
+    double *mean, *var, *samples;
+};
+hipError_t launch_moments(const DevScene& sc, const XScratch& xs, const CamDev& cam, int w, int h, const MomentsIO& io,
+                          hipStream_t stream);
 
 // ---- gi_mode_r.hip: the Mode R kernels, k_trace_ray, k_box_kat ----
 RKernel r_kernel_choice(const DevScene& sc, const gi_opts& o);
@@ -85,7 +96,7 @@ hipError_t launch_aov(const DevScene& sc, const XKernelCfg& c, const CamDev& cam
 hipError_t launch_cam_rays(const CamDev& cam, int x0, int y0, int cols, int rows, double* rays, hipStream_t stream);
 void wf_variant(const DevScene& sc, const XKernelCfg& c, int32_t out[6]);
 
-// ---- gi_denoise.hip: k_dn_prep, k_dn_level ----
+// ---- gi_denoise.hip: k_dn_prep, k_dn_level, k_dnv_g, k_dnv_level ----
 // One call of the denoiser (gi_denoise*): the window [x0, x0 + cols) x [y0, y0 + rows) of the frame, its
 // input planes and outputs, device pointers, row-major over the window; alb is read only with the albedo
 // stop; a null output is not written.
@@ -97,5 +108,15 @@ struct DnIO {
 };
 long long dn_scratch_bytes(long long n_px, int levels, bool albedo_stop);   // host only
 hipError_t launch_denoise(const CamDev& cam, const DnIO& io, const gi_denoise_params& p, void* scratch, hipStream_t stream);
+// One call of the variance-guided denoiser (gi_denoise_var*; k_dn_prep, k_dnv_g, k_dnv_level): as DnIO, with the
+// variance plane of the mean and its filtered output.
+struct DnvIO {
+    int x0, y0, cols, rows;
+    const double *rgb, *var, *t, *nrm, *alb;
+    double *out, *out_var;
+    uint8_t* out8;
+};
+long long dnv_scratch_bytes(long long n_px, int levels, bool albedo_stop);   // host only
+hipError_t launch_denoise_var(const CamDev& cam, const DnvIO& io, const gi_denoise_var_params& p, void* scratch, hipStream_t stream);
 
 }  // namespace gi

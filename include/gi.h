@@ -56,7 +56,7 @@
 extern "C" {
 #endif
 
-#define GI_ABI_VERSION 17
+#define GI_ABI_VERSION 18
 
 typedef enum gi_status {
     GI_OK = 0,
@@ -414,8 +414,8 @@ int gi_camera_rays(const gi_camera* cam, const gi_aov_frame* frame, double* rays
  *              gi_denoise_scratch_bytes, a NULL or not 16-byte aligned device scratch.  An empty window
  *              launches nothing and returns GI_OK.  gi_denoise_scratch_bytes (host only, no device): the
  *              bytes, or a negative gi_status for a bad frame or parameters (0 for an empty window).
- * Not provided: temporal accumulation, variance-guided sigmas, albedo demodulation, Mode R frames,
- * shard-packed buffers / gi_multi. */
+ * Not provided: temporal accumulation, albedo demodulation, Mode R frames, shard-packed buffers / gi_multi
+ * (a per-pixel colour stop from the samples' variance: gi_denoise_var* below). */
 #define GI_DENOISE_ALBEDO_STOP 1u  /* a tap contributes only if its albedo equals the centre's (three fp64 ==) */
 typedef struct gi_denoise_params {
     int32_t levels;           /* 1..8 a-trous levels, level i has step 2^i */
@@ -437,6 +437,89 @@ int64_t gi_denoise_scratch_bytes(const gi_aov_frame* frame, const gi_denoise_par
 int gi_denoise_device(const gi_camera* cam, const gi_aov_frame* frame, const gi_denoise_params* p,
                       const gi_denoise_io* d_io, void* d_scratch, int64_t scratch_bytes, void* stream);
 int gi_denoise(const gi_camera* cam, const gi_aov_frame* frame, const gi_denoise_params* p, const gi_denoise_io* io);
+
+/* ---- sample moments of the retained Mode X frame (ABI 18) -----------------------------------------
+ * How noisy is each pixel?  For spp > 1 every Mode X form keeps each listed pixel's per-sample radiance rows in
+ * the scene's scratch; these calls read them back as per-pixel moments.
+ *
+ * The retained frame is the scene's last render if that render was Mode X with spp > 1 and shard_count == 1,
+ * a whole frame (gi_render_device, or gi_render with one band: band_rows 0 or >= h), and was issued
+ * successfully; n is the number of samples rendered so far -- the last pass's sample_end, or spp for a one-shot
+ * frame.  Any other render of the scene (Mode R, spp == 1, sharded or banded ones included) and a failed render
+ * clear the record.  gi_frame_samples_info (host only) reports the retained frame's w, h, n and spp (any pointer
+ * may be NULL); GI_ERR_ARG without a retained frame.
+ *
+ * Outputs: row-major planes over the window of `frame`, as gi_render_aov lays them out; frame->w and frame->h
+ * must equal the retained frame's.  Per pixel, x_s is the radiance row of sample s < n: three doubles, unclamped.
+ * A pixel the classify pass resolved without traversal has no row: x_s = +0 for all s.
+ *   samples  rows*cols*n*3, [pixel][sample][3]: the rows themselves.
+ *   mean     rows*cols*3: per channel sum = +0; sum = sum + x_s for s = 0 .. n-1 in order; mean = sum / (double)n.
+ *            It is the render's own sum: min(mean, 1) is the delivered frame bit for bit.
+ *   var      rows*cols*3: the sample variance OF THE MEAN, two-pass.  Per channel m2 = +0; for s = 0 .. n-1 in
+ *            order d = x_s - mean, m2 = m2 + d d (one multiply, then one add, not contracted);
+ *            var = (m2 / (double)(n-1)) / (double)n.
+ *   Outputs    any pointer may be NULL and is then not written; all three NULL is GI_ERR_ARG.
+ *   Arguments  GI_ERR_ARG for a NULL scene, frame or gi_moments; without a retained frame; for n < 2 (a first
+ *              pass ending at sample 1); for a frame whose w, h are not the retained frame's, or a bad frame or
+ *              window as gi_render_aov judges them.  An empty window launches nothing and returns GI_OK.
+ * Ordering: unlike the ray queries these calls read the scene's Mode X scratch.  They run under the scene's
+ * mutex and are ordered on the device with the scene's renders in both directions: behind the scene's previous
+ * render, and the scene's next render (which overwrites the rows) behind them, whatever streams are used.  They
+ * are not renders: nothing of the progressive-frame state is touched, and a call between two passes does not
+ * end the frame.
+ * gi_frame_moments_device takes device pointers and is asynchronous on `stream`: no allocation, no copy, no host
+ * synchronisation.  gi_frame_moments does the same into host buffers (stage, launch, copy back), synchronous.
+ * Not provided: sharded or banded frames, gi_multi, Mode R. */
+typedef struct gi_moments { double* mean; double* var; double* samples; } gi_moments;
+int gi_frame_samples_info(gi_scene* scene, int32_t* w, int32_t* h, int32_t* n, int32_t* spp);
+int gi_frame_moments_device(gi_scene* scene, const gi_aov_frame* frame, const gi_moments* d_out, void* stream);
+int gi_frame_moments(gi_scene* scene, const gi_aov_frame* frame, const gi_moments* out);
+
+/* ---- variance-guided denoiser (ABI 18) -------------------------------------------------------------
+ * gi_denoise's filter with the colour stop per pixel from the variance of the mean (gi_moments.var) instead of
+ * one sigma_c for the frame.  Unchanged from gi_denoise: the fp64 rules, the window, validity and albedo-stop
+ * rules, the 25 taps with dy outer and dx inner, H, w_n, w_p, the centre tap, the final min(c, 1) and quantize.
+ * c^0 = rgb, V^0 = var.  At level i (step s = 2^i), for a valid pixel p:
+ *   prefiltered variance   v_q = (V_q.r + V_q.g) + V_q.b;  sum_k = 0; sum_v = 0;
+ *       for dy = -1..1 (outer), dx = -1..1 (inner): q = p + (dx, dy) -- step 1 at every level -- skipped if q is
+ *       outside the window or invalid (no albedo test here); k = G[dx+1] G[dy+1], G = {1/4, 1/2, 1/4};
+ *       sum_k += k; sum_v += k v_q.   g_p = sum_v / sum_k.
+ *   per-pixel stop         sigma2_p = (sigma_v sigma_v) g_p + var_floor (two multiplies, then the add); where
+ *       sigma_v sigma_v is +inf, sigma2_p = +inf whatever g_p is (no colour stop, also where g_p is 0).
+ *       The level's w_c = 1 / (1 + e.e / sigma2_p): no 2^-i shrink, the variance falls by itself.
+ *   variance propagation   beside sum_c += wt c_q, per channel sum_V += (wt wt) V_q;
+ *       c^{i+1}_p = sum_c / sum_w,  V^{i+1}_p = sum_V / (sum_w sum_w).
+ * Invalid pixels pass c and V through unchanged.  out_var = V^levels (not clamped).  The caller's planes are
+ * trusted as in gi_denoise: a negative or non-finite var gives unspecified pixels, never a fault.
+ * Defaults that serve the first passes of a Cornell-like frame: README.md "Sample moments / variance-guided
+ * denoiser".  The _device and host forms, the scratch and the argument rules are gi_denoise's, with sigma_v in
+ * sigma_c's place: GI_ERR_ARG also for a var_floor that is not finite and > 0, a NULL var, all three outputs
+ * NULL, out_rgb equal to rgb or out_var equal to var.
+ * Not provided: temporal accumulation, albedo demodulation, Mode R frames, shard-packed buffers / gi_multi. */
+typedef struct gi_denoise_var_params {
+    int32_t levels;           /* 1..8 */
+    int32_t normal_pow_log2;  /* 0..7 */
+    uint32_t flags;           /* GI_DENOISE_* */
+    int32_t reserved;         /* 0 */
+    double sigma_v;           /* > 0, +inf = no colour stop */
+    double sigma_p;           /* > 0, +inf = no plane stop */
+    double var_floor;         /* > 0, finite: added to every pixel's sigma2 */
+} gi_denoise_var_params;
+typedef struct gi_denoise_var_io {
+    const double* rgb;        /* rows*cols*3: gi_moments.mean (or the frame) */
+    const double* var;        /* rows*cols*3: gi_moments.var */
+    const double* t;          /* rows*cols: gi_aov.t */
+    const double* normal;     /* rows*cols*3: gi_aov.normal */
+    const double* albedo;     /* rows*cols*3: gi_aov.albedo; may be NULL without GI_DENOISE_ALBEDO_STOP */
+    double* out_rgb;          /* rows*cols*3, may be NULL */
+    double* out_var;          /* rows*cols*3, may be NULL */
+    uint8_t* out_rgb8;        /* rows*cols*3, may be NULL */
+} gi_denoise_var_io;
+int64_t gi_denoise_var_scratch_bytes(const gi_aov_frame* frame, const gi_denoise_var_params* p);
+int gi_denoise_var_device(const gi_camera* cam, const gi_aov_frame* frame, const gi_denoise_var_params* p,
+                          const gi_denoise_var_io* d_io, void* d_scratch, int64_t scratch_bytes, void* stream);
+int gi_denoise_var(const gi_camera* cam, const gi_aov_frame* frame, const gi_denoise_var_params* p,
+                   const gi_denoise_var_io* io);
 
 /* Average duration in ms of the dominant kernel over the scene's renders issued with GI_FLAG_TIME
  * since the previous call (waits for the last one; *n = how many, may be NULL), then resets.
