@@ -61,6 +61,7 @@ FLAG_X_NO_SHADOW = 8   # Mode X, tests only: no shadow rays (reduces depth-1 Mod
 FLAG_X_WF = 16   # Mode X: the wavefront form (one launch per bounce over compacted path queues, gi_wf.hip)
 FLAG_X_MEGA = 32   # Mode X: the persistent path-state kernel k_mode_x
 FLAG_X_SEG = 64   # Mode X: the segment-synchronous persistent form k_seg (no form flag: chosen per launch)
+FLAG_X_ALL_LEAVES = 128   # Mode X, tests only: shadow queries visit every leaf of the flat table (DeviceScene.shadow_leaves)
 KAT_X_TREE, KAT_X_HBM = 1, 2   # gi_kat_x_query's flags
 X_FORMS = ("k_mode_x", "k_wf_bounce", "k_seg")   # gi_scene_x_form's values
 R_KERNELS = ("k_mode_r", "k_rf_walk", "k_mode_r_batch")   # gi_scene_r_kernel's (1: the flat phases)
@@ -73,7 +74,7 @@ STAT_X_IT_RS, STAT_X_LN_RS, STAT_X_IT_ST, STAT_X_LN_ST = 20, 21, 22, 23
 STAT_R_PAIRS, STAT_R_OVF_TILES = 24, 25
 STATS_N = 26
 TILE = 8
-ABI_VERSION = 18
+ABI_VERSION = 19
 RAY_DOUBLES = 8   # a ray record of the batched queries: o[3], d[3], tmax, reserved (gi.h GI_RAY_DOUBLES)
 # the feature buffers of DeviceScene.render_aov (gi.h gi_aov, in its field order): name -> (dtype, trailing shape)
 AOV_OUTPUTS = ("t", "normal", "albedo", "prim", "entity", "uv")
@@ -176,7 +177,7 @@ TILE_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ct
 
 EXPORTS = ["gi_abi_version", "gi_last_error", "gi_camera_init", "gi_scene_create", "gi_scene_destroy",
            "gi_scene_get_info", "gi_render", "gi_render_device", "gi_shard_tiles", "gi_unshard_device",
-           "gi_trace_ray", "gi_kat_expbox", "gi_kat_x_query", "gi_kat_x_variant", "gi_kat_x_texel", "gi_scene_kernel_ms", "gi_scene_x_form", "gi_scene_seg_ring", "gi_scene_r_kernel", "gi_octree_create", "gi_octree_destroy",
+           "gi_trace_ray", "gi_kat_expbox", "gi_kat_x_query", "gi_kat_x_variant", "gi_kat_x_texel", "gi_scene_kernel_ms", "gi_scene_x_form", "gi_scene_seg_ring", "gi_scene_shadow_leaves", "gi_scene_r_kernel", "gi_octree_create", "gi_octree_destroy",
            "gi_octree_intersect", "gi_multi_create", "gi_multi_destroy", "gi_multi_info", "gi_multi_render", "gi_device_count",
            "gi_device_list", "gi_build_id", "gi_obj_parse", "gi_intersect", "gi_occluded", "gi_intersect_device",
            "gi_occluded_device", "gi_render_aov", "gi_render_aov_device", "gi_camera_rays", "gi_camera_rays_device",
@@ -249,6 +250,8 @@ def lib():
         L.gi_scene_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)]
         L.gi_scene_x_form.argtypes = [vp, ctypes.POINTER(Opts), ctypes.POINTER(ctypes.c_int32)]
         L.gi_scene_seg_ring.argtypes = [vp, ctypes.POINTER(Opts), ctypes.POINTER(ctypes.c_int32)]
+        L.gi_scene_shadow_leaves.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                             ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
         L.gi_scene_r_kernel.argtypes = [vp, ctypes.POINTER(Opts), ctypes.POINTER(ctypes.c_int32)]
         L.gi_octree_create.argtypes = [ctypes.POINTER(SceneDesc), ctypes.POINTER(vp)]
         L.gi_octree_destroy.argtypes = [vp]
@@ -634,6 +637,16 @@ class DeviceScene:
         f = ctypes.c_int32()
         _check(lib().gi_scene_seg_ring(self._h, ctypes.byref(o), ctypes.byref(f)), "gi_scene_seg_ring")
         return bool(f.value)
+
+    def shadow_leaves(self, light, cam_pos):
+        """(boundary mask, live mask) over the scene's flat leaf table for a Mode X render with this light
+        from this camera position: bit k of the first is set when leaf k lies in a plane with the whole
+        scene on one side, bit k of the second when the render's shadow queries visit leaf k (the light
+        could be occluded by it) -- gi_scene_shadow_leaves.  (0, 0) without the flat query."""
+        b, m = ctypes.c_uint32(), ctypes.c_uint32()
+        _check(lib().gi_scene_shadow_leaves(self._h, _d3(light), _d3(cam_pos), ctypes.byref(b), ctypes.byref(m)),
+               "gi_scene_shadow_leaves")
+        return b.value, m.value
 
     def r_kernel(self, flags=0) -> str:
         """The Mode R kernel a render would run: "k_mode_r" (one lane per pixel), "k_rf_walk" (the flat

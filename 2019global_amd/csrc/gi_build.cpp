@@ -493,6 +493,8 @@ void assign_plane_groups(HostScene& hs) {
     hs.x_skip_b = 2.0;   // > 1 >= |d . n|: no skip
     for (XPrim& p : hs.xprims) p.pad[0] = kXNoPlane;
     for (XWNode& w : hs.xwnodes) memset(w.pad, 0xFF, sizeof w.pad);
+    hs.x_planes.clear();
+    hs.x_tau = 0.0;
     double E = 0.0;
     for (const XPrim& p : hs.xprims)
         for (int k = 0; k < 3; ++k) {
@@ -546,7 +548,10 @@ void assign_plane_groups(HostScene& hs) {
         tau = std::max(tau, dev);
         s_min = std::min(s_min, s);
     }
+    hs.x_ext = E;
     if (groups.empty()) return;
+    hs.x_tau = tau;
+    for (const G& g : groups) hs.x_planes.push_back(HostScene::XPlane{{g.n.x, g.n.y, g.n.z}, g.off});
     for (XWNode& w : hs.xwnodes) {
         uint8_t* b = reinterpret_cast<uint8_t*>(w.pad);
         for (int c = 0; c < 8; ++c) {
@@ -588,6 +593,76 @@ void build_xflat(HostScene& hs) {
     }
     hs.x_flat_ok = ok && hs.xflat.size() <= (size_t)GI_XFLAT_MAX;
     hs.x_fan_all = !hs.xflat.empty() && (size_t)hs.n_fan_leaves == hs.xflat.size();
+    mark_boundary_leaves(hs);
+}
+
+// Boundary leaves (DESIGN.md §5 "light-dead leaves"): a leaf of the flat table all of whose records are one
+// plane group, with every primitive of the scene on one closed side of the group's plane to within tau, the
+// groups' measured coplanarity.  Primitives are taken by their own geometry -- a triangle's vertices, the
+// corners of a sphere's bounding cube -- not by their XBox records, whose outward padding of 1e-5 extents
+// reaches across the very plane a wall lies in.  x_dead_c is the bound derived there: a light at least
+// delta = x_dead_c * ldist_max from the plane, on the scene's side, is occluded by no record of the leaf.
+// Every triangle's smallest-angle sine enters it (s_all, not only the groups' s_min): a hit point computed on
+// a sliver next to a wall may lie behind the wall by that sliver's error.
+void mark_boundary_leaves(HostScene& hs) {
+    hs.xflat_plane.assign(hs.xflat.size(), XLeafPlane{});
+    hs.x_dead_c = INFINITY;
+    if (!hs.x_flat_ok || hs.x_planes.empty()) return;
+    const double tau = hs.x_tau;
+    double s_all = 1.0;
+    // per plane group: the least and the greatest n . x - c over the scene
+    std::vector<double> lo(hs.x_planes.size(), INFINITY), hi(hs.x_planes.size(), -INFINITY);
+    for (const XPrim& p : hs.xprims) {
+        V3 pts[8];
+        int npt = 0;
+        if (p.kind == 0) {
+            const V3 v0 = ld3(p.a), e1 = ld3(p.b), e2 = ld3(p.c), e3 = e2 - e1;
+            pts[0] = v0; pts[1] = v0 + e1; pts[2] = v0 + e2;
+            npt = 3;
+            const V3 cr = cross(e1, e2);
+            const double area2 = std::sqrt(dot(cr, cr)), l1 = std::sqrt(dot(e1, e1)), l2 = std::sqrt(dot(e2, e2)),
+                         l3 = std::sqrt(dot(e3, e3));
+            if (area2 > 0.0 && std::isfinite(area2))   // (a triangle without area is hit by no ray: det == 0)
+                s_all = std::min(s_all, std::min(std::min(area2 / (l1 * l2), area2 / (l1 * l3)), area2 / (l2 * l3)));
+        } else {
+            for (int k = 0; k < 8; ++k)
+                pts[k] = v3(p.a[0] + ((k & 1) ? p.b[0] : -p.b[0]), p.a[1] + ((k & 2) ? p.b[0] : -p.b[0]), p.a[2] + ((k & 4) ? p.b[0] : -p.b[0]));
+            npt = 8;
+        }
+        for (size_t g = 0; g < hs.x_planes.size(); ++g) {
+            const HostScene::XPlane& pl = hs.x_planes[g];
+            for (int k = 0; k < npt; ++k) {
+                const double h = dot(ld3(pl.n), pts[k]) - pl.c;   // (NaN: neither side holds below)
+                lo[g] = std::isnan(h) ? -INFINITY : std::min(lo[g], h);
+                hi[g] = std::isnan(h) ? INFINITY : std::max(hi[g], h);
+            }
+        }
+    }
+    bool any = false;
+    for (size_t k = 0; k < hs.xflat.size(); ++k) {
+        const int g = hs.xflat[k].group;
+        if (g == kXNoPlane || (size_t)g >= hs.x_planes.size()) continue;
+        XLeafPlane& r = hs.xflat_plane[k];
+        for (int a = 0; a < 3; ++a) r.n[a] = hs.x_planes[g].n[a];
+        r.c = hs.x_planes[g].c;
+        r.sides = (lo[g] >= -tau ? 1 : 0) | (hi[g] <= tau ? 2 : 0);
+        any = any || r.sides != 0;
+    }
+    if (!any || !(s_all > 0.0)) return;
+    // delta / ldist_max = K (2 eps + 4 u E / s) / MX_TMIN, eps = 32 u E / s + tau
+    const double K = 2000.0, u = 0x1.0p-53, tmin = 1e-7, E = hs.x_ext;
+    const double eps = 32.0 * u * E / s_all + tau;
+    hs.x_dead_c = K * (2.0 * eps + 4.0 * u * E / s_all) / tmin;
+}
+
+XShadowLeaves shadow_leaves_of(const HostScene& hs) {
+    XShadowLeaves sl;
+    if (!hs.x_flat_ok || hs.xflat_plane.size() != hs.xflat.size() || hs.xflat.size() > (size_t)GI_XFLAT_MAX) return sl;
+    sl.n = (int32_t)hs.xflat.size();
+    for (int k = 0; k < sl.n; ++k) sl.pl[k] = hs.xflat_plane[(size_t)k];
+    sl.dead_c = hs.x_dead_c;
+    sl.ext = hs.x_ext;
+    return sl;
 }
 
 bool build_host_scene(const gi_scene_desc& desc, HostScene& hs, std::string& err) {

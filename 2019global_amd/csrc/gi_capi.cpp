@@ -552,6 +552,7 @@ int scene_create_on(const gi_scene_desc* desc, int device, gi_scene** out) {
             d.x_far_r = std::isinf(d.x_far_r) ? m : std::max(d.x_far_r, m);
         }
     if ((e = x_launch_config(d, device, s->xcfg)) != hipSuccess) return hip_fail(e, "occupancy query");
+    s->xcfg.shadow = shadow_leaves_of(s->host);   // the boundary leaves a launch's light is tested against
     *out = s.release();
     return GI_OK;
 }
@@ -778,6 +779,19 @@ int gi_scene_x_form(gi_scene* s, const gi_opts* o, int32_t* form) {
         if (!s || !o || !form) return fail(GI_ERR_ARG, "null argument");
         std::lock_guard<std::mutex> lk(s->mu);
         *form = x_form_choice(s->dev, s->xcfg, *o);
+        return GI_OK;
+    });
+}
+
+int gi_scene_shadow_leaves(gi_scene* s, const double* light, const double* cam_pos, uint32_t* boundary_mask, uint32_t* live_mask) {
+    return guard([&]() -> int {
+        if (!s || !light || !cam_pos || !boundary_mask || !live_mask) return fail(GI_ERR_ARG, "null argument");
+        std::lock_guard<std::mutex> lk(s->mu);
+        const XShadowLeaves& sl = s->xcfg.shadow;
+        const bool on = s->dev.x_flat != 0 && sl.n > 0;
+        *boundary_mask = on ? sl.boundary_mask() : 0u;
+        *live_mask = on ? (x_launch_live(s->dev, s->xcfg, v3(cam_pos[0], cam_pos[1], cam_pos[2]), v3(light[0], light[1], light[2]), 0u) & sl.table_mask())
+                        : 0u;
         return GI_OK;
     });
 }

@@ -1180,7 +1180,8 @@ hipError_t launch_mode_x(const DevScene& sc, const XLaunchCfg& xc, const CamDev&
         if (!xs.wcnt || (form == XFORM_WF && (!xs.wq[0] || !xs.wq[1] || xs.wcap <= 0))) return hipErrorInvalidValue;
         const bool seg = form == XFORM_SEG;
         const XKernelCfg c{xc.var, env.flat != 0, seg ? xc.seg_lds_bytes : xc.wf_lds_bytes, xc.wf_grid[seg ? WK_SEG : WK_BOUNCE]};
-        e = launch_wf(sc, c, form, cam, light, m.w, m.h, m.y0, o, rgb, rgb8, xs, sc.work + 1, stats ? st : nullptr, xf, stream,
+        e = launch_wf(sc, c, form, cam, light, m.w, m.h, m.y0, o, rgb, rgb8, xs, sc.work + 1, stats ? st : nullptr, xf,
+                      x_launch_live(sc, xc, cam.pos, light, o.flags), stream,
                       ev_begin, ev_end);
         if (e != hipSuccess) return e;
     } else {

@@ -86,7 +86,14 @@ hipError_t wf_occupancy(const DevScene& sc, WfKernel k, const XKernelCfg& c, int
 XKernelCfg x_query_cfg(const XLaunchCfg& xc, int flags, WfKernel k);
 hipError_t launch_wf(const DevScene& sc, const XKernelCfg& c, XForm form, const CamDev& cam, V3 light, int w, int h, int y0,
                      const gi_opts& o, double* rgb, uint8_t* rgb8, const XScratch& xs, const unsigned* n_list_dev,
-                     unsigned long long* stats, int xflags, hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end);
+                     unsigned long long* stats, int xflags, uint32_t live, hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end);
+// The live mask of a Mode X launch's shadow queries (gi_scene.h x_shadow_live): full unless the launch runs the
+// scene's flat query with shadow rays, without GI_FLAG_X_ALL_LEAVES, from a near camera.
+inline uint32_t x_launch_live(const DevScene& sc, const XLaunchCfg& xc, V3 cam_pos, V3 light, unsigned flags) {
+    const double L[3] = {light.x, light.y, light.z}, C[3] = {cam_pos.x, cam_pos.y, cam_pos.z};
+    const bool full = !sc.x_flat || (flags & (GI_FLAG_X_NO_SHADOW | GI_FLAG_X_ALL_LEAVES)) != 0;
+    return x_shadow_live(xc.shadow, L, C, (double)sc.x_far_r, full);
+}
 hipError_t launch_x_query_kat(const DevScene& sc, const XKernelCfg& c, V3 cam_pos, int n, const double* recs, int32_t* oi,
                               double* od, hipStream_t stream);
 hipError_t launch_x_texel_kat(const DevScene& sc, XVariant var, int n, int mode, const double* recs, int32_t* oi, double* od,

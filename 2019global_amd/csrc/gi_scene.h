@@ -154,6 +154,44 @@ struct XFlatLeaf {         // 32 bytes
     uint8_t fan;           // 1: its two records are a fan pair (gi_fan_pair.h fan_pair_ok); host-side only
 };
 static_assert(sizeof(XFlatLeaf) == 32, "XFlatLeaf layout");
+// A leaf of the flat table as a boundary of the scene (gi_build.cpp mark_boundary_leaves; DESIGN.md §5
+// "light-dead leaves"): every record of the leaf lies in the plane n . x = c (one plane group), and every
+// primitive of the scene on the closed side(s) named by `sides`.  A shadow ray toward a light that lies on
+// such a side, at least XShadowLeaves::delta from the plane, cannot be occluded by the leaf.
+struct XLeafPlane {
+    double n[3], c;
+    int32_t sides;         // bit 0: the scene lies in n . x - c >= -tau; bit 1: in n . x - c <= tau; 0: no boundary leaf
+    int32_t pad;
+};
+// The boundary leaves of a scene's table and the bound of the light-dead rule, as a launch reads them.
+struct XShadowLeaves {
+    int32_t n = 0;               // leaves of the table (0: the rule does not apply; every mask is full)
+    XLeafPlane pl[GI_XFLAT_MAX] = {};
+    double dead_c = INFINITY;    // delta(L) = dead_c * ldist_max(L)
+    double ext = 0.0;            // E: the largest |coordinate| of a primitive
+    // the least distance of the light from a boundary leaf's plane at which the leaf is dead: dead_c times a
+    // bound on the length of a shadow ray toward L (both ends within E of the origin, or L farther out)
+    double delta(const double* L) const {
+        const double lm = std::fmax(std::fabs(L[0]), std::fmax(std::fabs(L[1]), std::fabs(L[2])));
+        return dead_c * (1.7320508075688774 * (lm + ext));
+    }
+    uint32_t table_mask() const { return n >= 32 ? ~0u : (1u << n) - 1u; }
+    uint32_t boundary_mask() const {
+        uint32_t b = 0;
+        for (int k = 0; k < n; ++k) b |= pl[k].sides ? 1u << k : 0u;
+        return b;
+    }
+    // bit k: leaf k can occlude a shadow ray toward L (a NaN anywhere keeps the leaf)
+    uint32_t live_mask(const double* L) const {
+        const double dl = delta(L);
+        uint32_t live = table_mask();
+        for (int k = 0; k < n; ++k) {
+            const double s = (pl[k].n[0] * L[0] + pl[k].n[1] * L[1] + pl[k].n[2] * L[2]) - pl[k].c;
+            if (((pl[k].sides & 1) && s >= dl) || ((pl[k].sides & 2) && -s >= dl)) live &= ~(1u << k);
+        }
+        return live;
+    }
+};
 
 struct HostScene {
     // Mode R
@@ -198,11 +236,30 @@ struct HostScene {
     int32_t n_fan_leaves = 0;        // leaves of xflat that are fan pairs (XFlatLeaf::fan)
     bool x_fan_all = false;          // every leaf of xflat is one (and there is a leaf): wf_flat's TRI kernels run
                                      // one exact test per leaf where the first step decides (DevScene::x_fan)
+    struct XPlane { double n[3], c; };
+    std::vector<XPlane> x_planes;    // the plane groups' planes, by group id (assign_plane_groups)
+    double x_tau = 0.0, x_ext = 0.0; // their measured coplanarity tolerance; E, the largest |coordinate| of a primitive
+    std::vector<XLeafPlane> xflat_plane;   // per leaf of xflat: its boundary record (mark_boundary_leaves)
+    double x_dead_c = INFINITY;      // the light-dead rule's bound per unit of shadow-ray length (XShadowLeaves::dead_c)
 };
 // Builds every host structure of a scene from its description (gi_build.cpp); false: err says why.
 bool build_host_scene(const gi_scene_desc& desc, HostScene& hs, std::string& err);
 // Fills hs.xflat / x_flat_ok from hs.xwnodes (after assign_plane_groups: the group bytes are copied).
 void build_xflat(HostScene& hs);
+// Fills hs.xflat_plane / x_dead_c from xflat, the plane groups and the primitives (build_xflat calls it).
+void mark_boundary_leaves(HostScene& hs);
+// The launch's copy of them (empty unless the table fits the flat query).
+XShadowLeaves shadow_leaves_of(const HostScene& hs);
+// The 32-bit mask of table leaves a launch's shadow queries visit (the kernels' shadow_live argument; all ones: every leaf, the
+// dense loop): full when the rule does not apply to the launch -- the flat query is not the scene's, no shadow
+// rays, the test flag, or a far camera (max |cam| above far_r: the hit points of its primary rays carry the
+// camera's rounding, which the bound does not budget).
+inline uint32_t x_shadow_live(const XShadowLeaves& sl, const double* light, const double* cam_pos, double far_r, bool full) {
+    const double cm = std::fmax(std::fabs(cam_pos[0]), std::fmax(std::fabs(cam_pos[1]), std::fabs(cam_pos[2])));
+    if (full || sl.n == 0 || !(cm <= far_r)) return ~0u;
+    const uint32_t live = sl.live_mask(light);
+    return live == sl.table_mask() ? ~0u : live;
+}
 
 // Sets XWNode::exists from the child references (both Mode X builders call it last).
 inline void finalize_xwnodes(std::vector<XWNode>& w) {
@@ -373,6 +430,7 @@ struct XLaunchCfg {
     size_t wf_lds_bytes = 0; // gi_wf.hip's kernels (k_wf_bounce, k_cast, k_aov, the query KAT): dynamic LDS per workgroup
     size_t wf_tree_lds_bytes = 0;   //   the same for the tree walk where the flat query is the default (the KAT's flag)
     int wf_grid[WK_COUNT] = {};     //   and each kernel's resident workgroups (WK_SEG_RING: with the ring's LDS)
+    XShadowLeaves shadow;    // the scene's boundary leaves (gi_capi.cpp fills it from the host scene)
     bool seg_ring = false;   // k_seg refills from its per-wave ring: its LDS does not lower k_seg's resident workgroups
     size_t seg_lds_bytes = 0;//   k_seg's dynamic LDS: wf_lds_bytes, and the ring's bytes with seg_ring
 };

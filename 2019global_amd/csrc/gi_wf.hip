@@ -268,7 +268,7 @@ __device__ __forceinline__ bool flat_hit(const XFlatLeaf* r, F3 no, F3 ivf, int 
 // leaf where the first record's first step decides (gi_fan_pair.h) -- the same (t, primitive) as with both
 template <bool ANY, bool TRI>
 __device__ __forceinline__ int wf_flat(float far_r, const XFlatLeaf* tab, const uint32_t* pkw, int n, const XHot* H, V3 o, V3 d, double tmax, bool act,
-                                       double& t_out, uint32_t& nnode, uint32_t& nprim, uint32_t& nsteps, int skip, bool fan) {
+                                       double& t_out, uint32_t& nnode, uint32_t& nprim, uint32_t& nsteps, int skip, bool fan, uint32_t live) {
     const F3 of = ray_org32(o, d, far_r);
     const F3 ivf = inv_dir(d);
     const F3 no = neg_oiv(of, ivf);
@@ -309,7 +309,39 @@ __device__ __forceinline__ int wf_flat(float far_r, const XFlatLeaf* tab, const 
     };
     // four records at a time, written out: the wave masks of step() are convergent operations, which the
     // compiler does not unroll around when the trip count is a run-time value
+    // live (launch-uniform; the any hit of a path's shadow ray, x_segment): bit k clear -- leaf k cannot occlude
+    // this launch's light (gi_build.cpp mark_boundary_leaves) and is not read.  The set bits are visited in
+    // order, up to four records per round so that their scalar loads stay batched; before a leaf that follows
+    // g skipped ones the candidate mask moves up by g, and by the trailing gap at the end, so leaf k ends at
+    // bit n - 1 - k as in the dense loop.  All ones (every other caller, as a constant): the dense loop alone.
     int k0 = 0;
+    if (ANY && live != ~0u) {
+        uint32_t rem = live & (n >= 32 ? ~0u : (1u << n) - 1u);
+        int prev = -1;
+        auto sstep = [&](const u32x8 w, int k) {
+            m <<= (k - prev - 1) & 31;   // (m is 0 before the first visited leaf)
+            step(w, k);
+            prev = k;
+        };
+        while (rem != 0) {
+            const int ka = __builtin_ctz(rem);
+            rem &= rem - 1;
+            const int kb = rem ? __builtin_ctz(rem) : -1;
+            rem &= rem - 1;
+            const int kc = rem ? __builtin_ctz(rem) : -1;
+            rem &= rem - 1;
+            const int kd = rem ? __builtin_ctz(rem) : -1;
+            rem &= rem - 1;
+            const u32x8 w0 = flat_rec_uniform(tab, ka), w1 = flat_rec_uniform(tab, kb < 0 ? ka : kb);
+            const u32x8 w2 = flat_rec_uniform(tab, kc < 0 ? ka : kc), w3 = flat_rec_uniform(tab, kd < 0 ? ka : kd);
+            sstep(w0, ka);
+            if (kb >= 0) sstep(w1, kb);
+            if (kc >= 0) sstep(w2, kc);
+            if (kd >= 0) sstep(w3, kd);
+        }
+        m <<= (n - 1 - prev) & 31;
+        k0 = n;
+    }
     for (; k0 + 4 <= n; k0 += 4) {
         const u32x8 w0 = flat_rec_uniform(tab, k0), w1 = flat_rec_uniform(tab, k0 + 1);
         const u32x8 w2 = flat_rec_uniform(tab, k0 + 2), w3 = flat_rec_uniform(tab, k0 + 3);
@@ -543,8 +575,9 @@ __device__ __forceinline__ void wf_wave_steps(uint32_t n, uint64_t& it, uint64_t
 // quantised nodes carry no groups).
 template <bool ANY, bool LDS, bool SH, bool TRI, bool CN, bool FLAT>
 __device__ __forceinline__ int x_query(const DevScene& sc, const WFView& v, float far_r, const V3& o, const V3& d, double tmax,
-                                       bool act, double& t_out, uint32_t& nnode, uint32_t& nprim, uint32_t& st_steps, int skip) {
-    if constexpr (FLAT) return wf_flat<ANY, TRI>(far_r, v.FT, v.FP, sc.n_xflat, v.LH, o, d, tmax, act, t_out, nnode, nprim, st_steps, skip, sc.x_fan != 0);
+                                       bool act, double& t_out, uint32_t& nnode, uint32_t& nprim, uint32_t& st_steps, int skip,
+                                       uint32_t live = ~0u) {
+    if constexpr (FLAT) return wf_flat<ANY, TRI>(far_r, v.FT, v.FP, sc.n_xflat, v.LH, o, d, tmax, act, t_out, nnode, nprim, st_steps, skip, sc.x_fan != 0, live);
     else if constexpr (LDS) return wf_trace<ANY, true, false, SH, TRI, false>(far_r, v.LW, v.LH, o, d, tmax, act, v.nst, t_out, nnode, nprim, st_steps, skip);
     else if constexpr (CN) return wf_trace<ANY, false, false, SH, TRI, true>(far_r, sc.xcnodes, sc.xhot, o, d, tmax, act, v.nst, t_out, nnode, nprim, st_steps);
     else return wf_trace<ANY, false, false, SH, TRI, true>(far_r, sc.xwnodes, sc.xhot, o, d, tmax, act, v.nst, t_out, nnode, nprim, st_steps, skip);
@@ -577,7 +610,7 @@ template <bool STATS, bool LDS, bool SH, bool TRI, bool CN, bool FLAT, typename 
 __device__ __forceinline__ bool x_segment(const DevScene& sc, const WFView& v, const V3& light, int depth, bool no_shadow, bool act,
                                           const KeyF& id_of, V3& o, V3& d, V3& L, V3& T,
                                           uint32_t& nnode, uint32_t& nprim, uint32_t& nrays, WFSegStats& ws,
-                                          double skip_cos = 2.0, int* splane = nullptr, float far_r = INFINITY) {
+                                          double skip_cos = 2.0, int* splane = nullptr, float far_r = INFINITY, uint32_t live = ~0u) {
     uint32_t st_steps = 0;
     uint64_t c0 = STATS ? clock64() : 0;
     bool occl = false;
@@ -604,7 +637,7 @@ __device__ __forceinline__ bool x_segment(const DevScene& sc, const WFView& v, c
     if (!no_shadow) {
         double tdummy;
         const int skip_s = x_own_plane(h.pg, h.pn, Ld, skip_cos);
-        occl = x_query<true, LDS, SH, TRI, CN, FLAT>(sc, v, INFINITY, P, Ld, h.ldist, hit, tdummy, nnode, nprim, st_steps, skip_s) >= 0;
+        occl = x_query<true, LDS, SH, TRI, CN, FLAT>(sc, v, INFINITY, P, Ld, h.ldist, hit, tdummy, nnode, nprim, st_steps, skip_s, live) >= 0;
         if (STATS) wf_wave_steps(st_steps, ws.it_s, ws.ln_s);
     }
     if (STATS) {
@@ -675,7 +708,7 @@ __device__ __forceinline__ bool x_segment(const DevScene& sc, const WFView& v, c
 template <bool STATS, bool LDS, bool W4, bool SH, bool TRI, bool CN, bool FLAT>
 __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_WAVES) void k_wf_bounce(
     DevScene sc, CamDev cam, V3 light, TileMap m, int spp, int depth, uint64_t seed, int b, double* rgb, uint8_t* rgb8,
-    unsigned long long* stats, WFArgs a, WFQ qin, WFQ qout, int xflags) {
+    unsigned long long* stats, WFArgs a, WFQ qin, WFQ qout, int xflags, uint32_t shadow_live) {
     // the bounce's input length: bounce 0, the chunk's units of the work list; else the queue
     unsigned n_in;
     if (b == 0) {
@@ -751,7 +784,7 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
         const float far_r = ray_far_r(sc, cam.pos);   // (far cameras: gi_dev.h ray_org32)
         int splane = 254;
         const bool cont = x_segment<false, LDS, SH, TRI, CN, FLAT>(sc, v, light, depth, no_shadow, act, [&] { return PathId{key, smp, b}; }, o, d, L, T,
-                                                             nnode, nprim, nrays, ws, skip_cos, &splane, far_r);
+                                                             nnode, nprim, nrays, ws, skip_cos, &splane, far_r, shadow_live);
         // ---- live paths to the next bounce's queue: one atomic per wave, entries in lane order
         const unsigned long long mc = __ballot(cont);
         if (mc) {
@@ -845,10 +878,13 @@ __device__ __forceinline__ unsigned long long seg_uniform64(unsigned long long v
 // time by all 64 lanes.  Without it they make their units themselves, under the need
 // mask.  The launch's dynamic LDS carries kSegRingBytes behind the path slots only with RING.  (A
 // template parameter: as a run-time choice in one kernel the Cornell box's variant took 12 B of scratch.)
+// shadow_live: the table leaves the launch's shadow queries visit (gi_scene.h x_shadow_live; all ones: every
+// leaf).  The last argument, in the four bytes behind xflags that were padding: as a field of WFArgs it moved
+// the arguments behind it, and the kernels without the flat query compiled to other instructions.
 template <bool STATS, bool LDS, bool W4, bool SH, bool TRI, bool CN, bool FLAT, bool RING>
 __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_WAVES) void k_seg(
     DevScene sc, CamDev cam, V3 light, TileMap m, int spp, int depth, uint64_t seed, double* rgb, uint8_t* rgb8,
-    unsigned long long* stats, WFArgs a, int xflags) {
+    unsigned long long* stats, WFArgs a, int xflags, uint32_t shadow_live) {
     extern __shared__ int4 lds_dyn[];
     const WFView v = wf_stage<LDS, FLAT>(sc, lds_dyn);
     const bool no_shadow = (xflags & XF_NO_SHADOW) != 0;
@@ -987,7 +1023,7 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
         const bool cont = x_segment<STATS, LDS, SH, TRI, CN, FLAT>(
             sc, v, light, depth, no_shadow, live,
             [&] { return PathId{slot_get_u64(v.pl, 6), (unsigned)(slot_get_u64(v.pl, 7) >> 32), splane >> kSegPlaneBits}; },
-            o, d, L, T, nnode, nprim, nrays, ws, skip_cos, &splane, far_r);
+            o, d, L, T, nnode, nprim, nrays, ws, skip_cos, &splane, far_r, shadow_live);
         if (live) {
             if (cont) {
                 splane += 1 << kSegPlaneBits;   // the next bounce
@@ -1374,7 +1410,7 @@ hipError_t wf_occupancy(const DevScene& sc, WfKernel k, const XKernelCfg& c, int
 // c.flat is the launch's choice (xflags without XF_NO_FLAT).
 hipError_t launch_wf(const DevScene& sc, const XKernelCfg& c, XForm form, const CamDev& cam, V3 light, int w, int h, int y0,
                      const gi_opts& o, double* rgb, uint8_t* rgb8, const XScratch& xs, const unsigned* n_list_dev,
-                     unsigned long long* stats, int xflags, hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end) {
+                     unsigned long long* stats, int xflags, uint32_t live, hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end) {
     const TileMap m = make_map(w, h, o.shard_count, o.shard_index, y0);
     const int depth = o.depth;
     const int s0 = o.sample_end > 0 ? o.sample_begin : 0, s1 = o.sample_end > 0 ? o.sample_end : o.spp;
@@ -1391,9 +1427,9 @@ hipError_t launch_wf(const DevScene& sc, const XKernelCfg& c, XForm form, const 
         if (ev_begin) (void)hipEventRecord(ev_begin, stream);
         wf_dispatch(sc, c, stats != nullptr, [&](auto V) {
             if (xflags & XF_SEG_RING)   // (c.lds_bytes then holds the ring's: XLaunchCfg::seg_lds_bytes)
-                hipLaunchKernelGGL(seg_kernel<true>(V), grid, block, c.lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, rgb, rgb8, stats, a, xflags);
+                hipLaunchKernelGGL(seg_kernel<true>(V), grid, block, c.lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, rgb, rgb8, stats, a, xflags, live);
             else
-                hipLaunchKernelGGL(seg_kernel<false>(V), grid, block, c.lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, rgb, rgb8, stats, a, xflags);
+                hipLaunchKernelGGL(seg_kernel<false>(V), grid, block, c.lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, rgb, rgb8, stats, a, xflags, live);
         });
         if (ev_end) (void)hipEventRecord(ev_end, stream);
         return hipGetLastError();
@@ -1420,7 +1456,7 @@ hipError_t launch_wf(const DevScene& sc, const XKernelCfg& c, XForm form, const 
             qout.r = xs.wq[b & 1];
             qout.id = reinterpret_cast<uint2*>(xs.wid[b & 1]);
             wf_dispatch(sc, c, stats != nullptr, [&](auto V) {
-                hipLaunchKernelGGL(bounce_kernel(V), grid, block, c.lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, b, rgb, rgb8, stats, a, qin, qout, xflags);
+                hipLaunchKernelGGL(bounce_kernel(V), grid, block, c.lds_bytes, stream, sc, cam, light, m, o.spp, depth, o.seed, b, rgb, rgb8, stats, a, qin, qout, xflags, live);
             });
         }
     }

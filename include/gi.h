@@ -56,7 +56,7 @@
 extern "C" {
 #endif
 
-#define GI_ABI_VERSION 18
+#define GI_ABI_VERSION 19
 
 typedef enum gi_status {
     GI_OK = 0,
@@ -134,6 +134,9 @@ typedef enum gi_mode {
 #define GI_FLAG_X_SEG 64u        /* Mode X: the segment-synchronous persistent form (k_seg: every loop
                                     iteration one whole path segment per lane).  None of the three form
                                     flags: chosen per launch (GI_X_WF=0/1/2 overrides) */
+#define GI_FLAG_X_ALL_LEAVES 128u /* Mode X, test only (ABI 19): the shadow queries of the flat leaf query visit every
+                                    leaf of the table, also those the launch's light cannot be occluded by
+                                    (gi_scene_shadow_leaves); same frame bit for bit */
 
 typedef struct gi_opts {
     int32_t mode;          /* gi_mode */
@@ -535,6 +538,16 @@ int gi_scene_x_form(gi_scene* scene, const gi_opts* opts, int32_t* form);
  * GI_SEG_RING=0 is set in the environment; 0 = k_seg's lanes make their own units, or another form
  * or mode runs.  Frames are the same bit for bit either way. */
 int gi_scene_seg_ring(gi_scene* scene, const gi_opts* opts, int32_t* on);
+/* The boundary leaves of the scene's flat leaf table and the leaves a render's shadow queries visit (ABI 19;
+ * tests, bench labels).  *boundary_mask: bit k set when leaf k lies in a plane that has the whole scene on
+ * one closed side.  *live_mask: bit k set when the shadow queries of a Mode X render with light[3] from
+ * cam_pos[3] visit leaf k: every leaf of the table except the boundary leaves that have the light on the
+ * scene's side, farther from their plane than the scene's bound -- no shadow ray toward that
+ * light can cross them.  Every leaf for a camera farther out than 16 scene extents.  Both 0 for a scene that
+ * does not answer its queries from the table.  GI_FLAG_X_ALL_LEAVES and GI_FLAG_X_NO_SHADOW renders visit
+ * every leaf (the latter traces no shadow ray). */
+int gi_scene_shadow_leaves(gi_scene* scene, const double* light, const double* cam_pos, uint32_t* boundary_mask,
+                           uint32_t* live_mask);
 /* Mode R kernel a render of `scene` with `opts` would run (ABI 10; bench labels, tests): 0 = k_mode_r
  * (one lane per pixel: small scenes, GI_FLAG_R_DFS), 1 = the flat phases (k_rf_walk, k_rf_hit,
  * k_rf_scan, k_rf_reach, k_rf_shade; scenes of more than 4096 entities; their overflowed tiles by
