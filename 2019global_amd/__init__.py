@@ -27,6 +27,8 @@ those buffers (an edge-avoiding a-trous filter: a preview of the first progressi
 ``denoise_device`` on a HIP stream into caller-owned buffers.  ``DeviceScene.frame_moments`` returns the
 per-pixel sample mean, variance of the mean and per-sample radiance of the scene's retained Mode X frame, and
 ``denoise_var`` is the filter with its colour stop per pixel from that variance (``_device`` forms alike).
+``temporal`` / ``temporal_device`` reproject the previous frame's accumulated colour and variance onto a frame's
+first hits and blend them with it: the samples a moving camera would otherwise throw away.
 """
 from __future__ import annotations
 
@@ -48,6 +50,8 @@ __all__ = [
     "DenoiseParams", "DENOISE_ALBEDO_STOP", "denoise", "denoise_scratch_bytes", "denoise_device",
     "MOMENTS_OUTPUTS", "DenoiseVarParams", "DENOISE_VAR_OUTPUTS", "DENOISE_VAR_SIGMA_V", "DENOISE_VAR_FLOOR",
     "denoise_var", "denoise_var_scratch_bytes", "denoise_var_device",
+    "TemporalParams", "TemporalFrame", "TemporalOut", "TEMPORAL_PRIM_STOP", "TEMPORAL_OUTPUTS", "TEMPORAL_PLANES",
+    "temporal", "temporal_device",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -74,7 +78,7 @@ STAT_X_IT_RS, STAT_X_LN_RS, STAT_X_IT_ST, STAT_X_LN_ST = 20, 21, 22, 23
 STAT_R_PAIRS, STAT_R_OVF_TILES = 24, 25
 STATS_N = 26
 TILE = 8
-ABI_VERSION = 19
+ABI_VERSION = 20
 RAY_DOUBLES = 8   # a ray record of the batched queries: o[3], d[3], tmax, reserved (gi.h GI_RAY_DOUBLES)
 # the feature buffers of DeviceScene.render_aov (gi.h gi_aov, in its field order): name -> (dtype, trailing shape)
 AOV_OUTPUTS = ("t", "normal", "albedo", "prim", "entity", "uv")
@@ -172,6 +176,25 @@ class DenoiseVarIO(ctypes.Structure):
                 ("out_rgb8", ctypes.c_void_p)]
 
 
+TEMPORAL_PRIM_STOP = 1   # gi.h GI_TEMPORAL_PRIM_STOP
+TEMPORAL_OUTPUTS = ("rgb", "var", "len")   # gi.h gi_temporal_out, in its field order
+TEMPORAL_PLANES = ("rgb", "var", "t", "normal", "prim", "len")   # gi.h gi_temporal_frame, in its field order
+
+
+class TemporalParams(ctypes.Structure):
+    _fields_ = [("max_history", ctypes.c_int32), ("flags", ctypes.c_uint32), ("alpha_min", ctypes.c_double),
+                ("cos_min", ctypes.c_double), ("sigma_p", ctypes.c_double)]
+
+
+class TemporalFrame(ctypes.Structure):
+    _fields_ = [("rgb", ctypes.c_void_p), ("var", ctypes.c_void_p), ("t", ctypes.c_void_p), ("normal", ctypes.c_void_p),
+                ("prim", ctypes.c_void_p), ("len", ctypes.c_void_p)]
+
+
+class TemporalOut(ctypes.Structure):
+    _fields_ = [("rgb", ctypes.c_void_p), ("var", ctypes.c_void_p), ("len", ctypes.c_void_p)]
+
+
 TILE_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint8),
                            ctypes.POINTER(ctypes.c_double))
 
@@ -183,7 +206,8 @@ EXPORTS = ["gi_abi_version", "gi_last_error", "gi_camera_init", "gi_scene_create
            "gi_occluded_device", "gi_render_aov", "gi_render_aov_device", "gi_camera_rays", "gi_camera_rays_device",
            "gi_denoise_scratch_bytes", "gi_denoise_device", "gi_denoise",
            "gi_frame_samples_info", "gi_frame_moments_device", "gi_frame_moments",
-           "gi_denoise_var_scratch_bytes", "gi_denoise_var_device", "gi_denoise_var"]
+           "gi_denoise_var_scratch_bytes", "gi_denoise_var_device", "gi_denoise_var",
+           "gi_temporal_device", "gi_temporal"]
 
 _lib = None
 _lock = threading.Lock()
@@ -247,7 +271,11 @@ def lib():
                                             ctypes.POINTER(DenoiseVarIO), vp, ctypes.c_int64, vp]
         L.gi_denoise_var.argtypes = [ctypes.POINTER(CameraDesc), ctypes.POINTER(AovFrame), ctypes.POINTER(DenoiseVarParams),
                                      ctypes.POINTER(DenoiseVarIO)]
-        L.gi_scene_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)]
+        tp_args = [ctypes.POINTER(CameraDesc), ctypes.POINTER(CameraDesc), ctypes.POINTER(AovFrame), ctypes.POINTER(TemporalParams),
+                   ctypes.POINTER(TemporalFrame), ctypes.POINTER(TemporalFrame), ctypes.POINTER(TemporalOut)]
+        L.gi_temporal_device.argtypes = tp_args + [vp]
+        L.gi_temporal.argtypes = tp_args
+        L.gi_scene_kernel_ms.argtypes =[vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)]
         L.gi_scene_x_form.argtypes = [vp, ctypes.POINTER(Opts), ctypes.POINTER(ctypes.c_int32)]
         L.gi_scene_seg_ring.argtypes = [vp, ctypes.POINTER(Opts), ctypes.POINTER(ctypes.c_int32)]
         L.gi_scene_shadow_leaves.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
@@ -977,6 +1005,83 @@ def denoise_var_device(cam: "Camera", w: int, h: int, d_rgb: int, d_var: int, d_
     p = _denoise_var_params(levels, sigma_v, sigma_p, var_floor, normal_pow_log2, albedo_stop)
     _check(lib().gi_denoise_var_device(ctypes.byref(cam._c), ctypes.byref(f), ctypes.byref(p), ctypes.byref(io), d_scratch or None,
                                        int(scratch_bytes), stream or None), "gi_denoise_var_device")
+
+
+def _temporal_params(max_history, alpha_min, cos_min, sigma_p, prim_stop) -> TemporalParams:
+    return TemporalParams(int(max_history), TEMPORAL_PRIM_STOP if prim_stop else 0, float(alpha_min), float(cos_min), float(sigma_p))
+
+
+# temporal's defaults are starting values (README.md "Temporal accumulation": what they do on the Cornell box)
+def temporal(cam: "Camera", prev_cam: Optional["Camera"], w: int, h: int, cur: dict, hist: Optional[dict] = None, window=None,
+             max_history: int = 32, alpha_min: float = 0.0, cos_min: float = 0.9, sigma_p: float = 0.01, prim_stop: bool = True,
+             want=TEMPORAL_OUTPUTS) -> dict:
+    """The temporal accumulation of gi.h "temporal accumulation" over the window (x0, y0, x1, y1) of a w x h frame
+    (None: the whole frame), from host arrays (gi_temporal).  cur: the current frame's planes by name -- "rgb"
+    (rows, cols, 3) float64 (frame_moments' "mean", or the frame), "t" (rows, cols) and "normal" (rows, cols, 3)
+    float64 of render_aov for cam, "prim" (rows, cols) int32 with prim_stop, "var" (rows, cols, 3) float64 where the
+    variance is carried.  hist: the previous frame's planes for prev_cam -- the accumulated "rgb" (and "var"), that
+    frame's "t", "normal" (and "prim"), and "len" (rows, cols) int32, the samples accumulated per pixel; None (prev_cam
+    may be None too): the first frame, every valid pixel resets.  Returns the outputs named in want: "rgb" and "var"
+    (rows, cols, 3) float64, "len" (rows, cols) int32 -- with this frame's t, normal and prim the next call's hist.
+    ValueError for a wrong shape, a missing plane or a wrong want."""
+    want = tuple(want)
+    if not want or any(k not in TEMPORAL_OUTPUTS for k in want) or len(set(want)) != len(want):
+        raise ValueError(f"temporal: want is a non-empty selection of {TEMPORAL_OUTPUTS}")
+    f = _aov_frame(w, h, window)
+    rows, cols = f.y1 - f.y0, f.x1 - f.x0
+    if hist is not None and prev_cam is None:
+        raise ValueError("temporal: a history needs prev_cam")
+    kinds = {"rgb": (np.float64, (3,)), "var": (np.float64, (3,)), "t": (np.float64, ()), "normal": (np.float64, (3,)),
+             "prim": (np.int32, ()), "len": (np.int32, ())}
+
+    def planes(side, d, need):
+        missing = [k for k in need if d.get(k) is None]
+        if missing:
+            raise ValueError(f"temporal: {side} lacks {missing}")
+        got = {}
+        for k in need:
+            dt, tail = kinds[k]
+            a = np.ascontiguousarray(d[k], dt)
+            if a.size != rows * cols * (tail[0] if tail else 1):
+                raise ValueError(f"temporal: {side}[{k!r}] must hold {(rows, cols) + tail} {np.dtype(dt).name}")
+            got[k] = a
+        return got
+    need = ["rgb", "t", "normal"] + (["prim"] if prim_stop else []) + (["var"] if "var" in want else [])
+    c = planes("cur", cur, need)
+    hh = planes("hist", hist, need + ["len"]) if hist is not None else None
+    bufs = {"rgb": np.empty((rows, cols, 3), np.float64), "var": np.empty((rows, cols, 3), np.float64),
+            "len": np.empty((rows, cols), np.int32)}
+
+    def frame_of(d):   # (an empty window: valid addresses, apart from the outputs')
+        return TemporalFrame(**{k: (a.ctypes.data if a.size else _scratch_ptr()) for k, a in d.items()})
+    fc, fh = frame_of(c), (frame_of(hh) if hh is not None else None)
+    out = TemporalOut(**{k: (bufs[k].ctypes.data if bufs[k].size else _scratch_ptr() + 32) for k in want})
+    p = _temporal_params(max_history, alpha_min, cos_min, sigma_p, prim_stop)
+    _check(lib().gi_temporal(ctypes.byref(cam._c), ctypes.byref(prev_cam._c) if prev_cam is not None else None, ctypes.byref(f),
+                             ctypes.byref(p), ctypes.byref(fc), ctypes.byref(fh) if fh is not None else None, ctypes.byref(out)),
+           "gi_temporal")
+    return {k: bufs[k] for k in want}
+
+
+def temporal_device(cam: "Camera", prev_cam: Optional["Camera"], w: int, h: int, d_cur: dict, d_hist: Optional[dict] = None,
+                    d_out_rgb: int = 0, d_out_var: int = 0, d_out_len: int = 0, window=None, max_history: int = 32,
+                    alpha_min: float = 0.0, cos_min: float = 0.9, sigma_p: float = 0.01, prim_stop: bool = True,
+                    stream: int = 0) -> None:
+    """Asynchronous temporal of device planes into device outputs on the current device (gi_temporal_device); d_cur and
+    d_hist map the names of TEMPORAL_PLANES to device pointers (ints; a missing name or 0: null), d_hist None: the
+    first frame; an output of 0 is not written.  No scratch."""
+    f = _aov_frame(w, h, window)
+
+    def frame_of(d):
+        if any(k not in TEMPORAL_PLANES for k in d):
+            raise ValueError(f"temporal_device: the planes are named {TEMPORAL_PLANES}")
+        return TemporalFrame(**{k: (int(v) or None) for k, v in d.items() if v})
+    fc, fh = frame_of(d_cur), (frame_of(d_hist) if d_hist is not None else None)
+    out = TemporalOut(d_out_rgb or None, d_out_var or None, d_out_len or None)
+    p = _temporal_params(max_history, alpha_min, cos_min, sigma_p, prim_stop)
+    _check(lib().gi_temporal_device(ctypes.byref(cam._c), ctypes.byref(prev_cam._c) if prev_cam is not None else None, ctypes.byref(f),
+                                    ctypes.byref(p), ctypes.byref(fc), ctypes.byref(fh) if fh is not None else None, ctypes.byref(out),
+                                    stream or None), "gi_temporal_device")
 
 
 def devices_from_env(default=None):

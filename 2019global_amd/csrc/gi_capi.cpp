@@ -1324,6 +1324,103 @@ int gi_denoise_var(const gi_camera* cam, const gi_aov_frame* frame, const gi_den
     });
 }
 
+// ---- temporal accumulation (gi.h "temporal accumulation"; gi_temporal.hip k_temporal) ----
+// No scene, no state, no scratch: the caller's planes on the current device.
+namespace {
+// everything of a temporal call; *empty: the window holds no pixel
+int check_temporal(const gi_camera* cam, const gi_camera* prev_cam, const gi_aov_frame* frame, const gi_temporal_params* p,
+                   const gi_temporal_frame* cur, const gi_temporal_frame* hist, const gi_temporal_out* out, bool* empty) {
+    if (!p || !cur || !out) return fail(GI_ERR_ARG, "gi_temporal: null parameters, current frame or outputs");
+    int rc = check_aov_frame(cam, frame, empty);
+    if (rc) return rc;
+    if (hist) {
+        if (!prev_cam) return fail(GI_ERR_ARG, "gi_temporal: a history needs the previous camera");
+        bool e2 = false;
+        if ((rc = check_aov_frame(prev_cam, frame, &e2))) return rc;
+    }
+    if (p->max_history < 1) return fail(GI_ERR_ARG, "gi_temporal: max_history must be >= 1");
+    if (p->flags & ~GI_TEMPORAL_PRIM_STOP) return fail(GI_ERR_ARG, "gi_temporal: unknown flag");
+    if (!(p->alpha_min >= 0 && p->alpha_min <= 1)) return fail(GI_ERR_ARG, "gi_temporal: alpha_min outside [0, 1]");
+    if (!(p->cos_min >= -1 && p->cos_min <= 1)) return fail(GI_ERR_ARG, "gi_temporal: cos_min outside [-1, 1]");
+    if (!(p->sigma_p > 0)) return fail(GI_ERR_ARG, "gi_temporal: sigma_p must be > 0 (+inf: no plane stop)");
+    const bool stop = (p->flags & GI_TEMPORAL_PRIM_STOP) != 0;
+    if (!cur->rgb || !cur->t || !cur->normal) return fail(GI_ERR_ARG, "gi_temporal: null rgb, t or normal of the current frame");
+    if (hist && (!hist->rgb || !hist->t || !hist->normal || !hist->len)) return fail(GI_ERR_ARG, "gi_temporal: null rgb, t, normal or len of the history");
+    if (stop && (!cur->prim || (hist && !hist->prim))) return fail(GI_ERR_ARG, "gi_temporal: the prim stop needs the prim planes");
+    if (out->var && (!cur->var || (hist && !hist->var))) return fail(GI_ERR_ARG, "gi_temporal: out.var needs the var planes");
+    if (!out->rgb && !out->var && !out->len) return fail(GI_ERR_ARG, "gi_temporal: every output is null");
+    // the taps gather: no output may be an input
+    const void* outs[3] = {out->rgb, out->var, out->len};
+    const void* ins[11] = {cur->rgb, cur->var, cur->t, cur->normal, cur->prim,   // (cur.len is ignored)
+                           hist ? hist->rgb : nullptr, hist ? hist->var : nullptr, hist ? hist->t : nullptr,
+                           hist ? hist->normal : nullptr, hist ? hist->prim : nullptr, hist ? hist->len : nullptr};
+    for (const void* o : outs) {
+        if (!o) continue;
+        for (const void* q : ins)
+            if (o == q) return fail(GI_ERR_ARG, "gi_temporal: an output must not be an input plane");
+    }
+    return GI_OK;
+}
+TpIO tp_io(const gi_aov_frame& f, const gi_temporal_frame& cur, const gi_temporal_frame* hist, const gi_temporal_out& out) {
+    return TpIO{f.x0, f.y0, f.x1 - f.x0, f.y1 - f.y0, cur, hist ? *hist : gi_temporal_frame{}, out};
+}
+}  // namespace
+
+int gi_temporal_device(const gi_camera* cam, const gi_camera* prev_cam, const gi_aov_frame* frame, const gi_temporal_params* p,
+                       const gi_temporal_frame* d_cur, const gi_temporal_frame* d_hist, const gi_temporal_out* d_out, void* stream) {
+    return guard([&]() -> int {
+        bool empty = false;
+        const int rc = check_temporal(cam, prev_cam, frame, p, d_cur, d_hist, d_out, &empty);
+        if (rc || empty) return rc;
+        const CamDev c = make_cam(*cam, frame->w);
+        const hipError_t e = launch_temporal(c, d_hist ? make_cam(*prev_cam, frame->w) : c, tp_io(*frame, *d_cur, d_hist, *d_out), *p,
+                                             static_cast<hipStream_t>(stream));
+        return e == hipSuccess ? GI_OK : hip_fail(e, "gi_temporal launch");
+    });
+}
+
+int gi_temporal(const gi_camera* cam, const gi_camera* prev_cam, const gi_aov_frame* frame, const gi_temporal_params* p,
+                const gi_temporal_frame* cur, const gi_temporal_frame* hist, const gi_temporal_out* out) {
+    return guard([&]() -> int {
+        bool empty = false;
+        const int rc = check_temporal(cam, prev_cam, frame, p, cur, hist, out, &empty);
+        if (rc || empty) return rc;
+        const size_t m = (size_t)(frame->x1 - frame->x0) * (size_t)(frame->y1 - frame->y0), b1 = m * sizeof(double), b3 = 3 * b1,
+                     bi = m * sizeof(int32_t);
+        const bool stop = (p->flags & GI_TEMPORAL_PRIM_STOP) != 0, var = out->var != nullptr;
+        // the planes the kernel reads, staged: {host plane, bytes, needed}
+        struct Plane { const void* host; size_t bytes; bool on; DevBuf dev; };
+        Plane in[11] = {{cur->rgb, b3, true, {}}, {cur->var, b3, var, {}}, {cur->t, b1, true, {}}, {cur->normal, b3, true, {}},
+                        {cur->prim, bi, stop, {}},
+                        {hist ? hist->rgb : nullptr, b3, hist != nullptr, {}}, {hist ? hist->var : nullptr, b3, hist && var, {}},
+                        {hist ? hist->t : nullptr, b1, hist != nullptr, {}}, {hist ? hist->normal : nullptr, b3, hist != nullptr, {}},
+                        {hist ? hist->prim : nullptr, bi, hist && stop, {}}, {hist ? hist->len : nullptr, bi, hist != nullptr, {}}};
+        DevBuf orgb, ovar, olen;
+        hipError_t e = hipSuccess;
+        for (Plane& q : in)
+            if (e == hipSuccess && q.on) e = q.dev.alloc(q.bytes);
+        if (e == hipSuccess && out->rgb) e = orgb.alloc(b3);
+        if (e == hipSuccess && out->var) e = ovar.alloc(b3);
+        if (e == hipSuccess && out->len) e = olen.alloc(bi);
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc (temporal staging)");
+        for (Plane& q : in)
+            if (e == hipSuccess && q.on) e = hipMemcpy(q.dev.p, q.host, q.bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return hip_fail(e, "gi_temporal");
+        auto dp = [&](int k) { return static_cast<const double*>(in[k].dev.p); };
+        auto ip = [&](int k) { return static_cast<const int32_t*>(in[k].dev.p); };
+        const gi_temporal_frame dcur{dp(0), dp(1), dp(2), dp(3), ip(4), nullptr};
+        const gi_temporal_frame dhist{dp(5), dp(6), dp(7), dp(8), ip(9), ip(10)};
+        const gi_temporal_out dout{static_cast<double*>(orgb.p), static_cast<double*>(ovar.p), static_cast<int32_t*>(olen.p)};
+        const CamDev c = make_cam(*cam, frame->w);
+        e = launch_temporal(c, hist ? make_cam(*prev_cam, frame->w) : c, tp_io(*frame, dcur, hist ? &dhist : nullptr, dout), *p, nullptr);
+        if (e != hipSuccess) return hip_fail(e, "gi_temporal launch");
+        if (out->rgb) e = hipMemcpy(out->rgb, orgb.p, b3, hipMemcpyDeviceToHost);   // (synchronous copies on the launch's stream)
+        if (e == hipSuccess && out->var) e = hipMemcpy(out->var, ovar.p, b3, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && out->len) e = hipMemcpy(out->len, olen.p, bi, hipMemcpyDeviceToHost);
+        return e == hipSuccess ? GI_OK : hip_fail(e, "gi_temporal");
+    });
+}
+
 int gi_kat_expbox(int n, const double* recs, int32_t* out) {
     return guard([&]() -> int {
         if (n < 0 || (n > 0 && (!recs || !out))) return fail(GI_ERR_ARG, "bad arguments");

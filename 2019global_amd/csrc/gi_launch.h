@@ -1,4 +1,4 @@
-// gi_launch.h — the host functions that libgi's kernel units (gi_kernels.hip, gi_mode_r.hip, gi_wf.hip, gi_denoise.hip)
+// gi_launch.h — the host functions that libgi's kernel units (gi_kernels.hip, gi_mode_r.hip, gi_wf.hip, gi_denoise.hip, gi_temporal.hip)
 // define for each other and for gi_capi.cpp.  The only place where a cross-unit function is declared: the
 // unit that defines one and the units that call it all include this header.  Host-only, no device code.
 #pragma once
@@ -125,5 +125,17 @@ struct DnvIO {
 };
 long long dnv_scratch_bytes(long long n_px, int levels, bool albedo_stop);   // host only
 hipError_t launch_denoise_var(const CamDev& cam, const DnvIO& io, const gi_denoise_var_params& p, void* scratch, hipStream_t stream);
+
+// ---- gi_temporal.hip: k_temporal ----
+// One call of the temporal accumulation (gi_temporal*): the window [x0, x0 + cols) x [y0, y0 + rows) of the frame,
+// the current frame's planes, the history's (hist.rgb null: no history, every valid pixel resets; `prev` is then
+// not read) and the outputs, device pointers, row-major over the window; a null output is not written.  The prim
+// planes are read only with GI_TEMPORAL_PRIM_STOP, the var planes only where out.var is written.
+struct TpIO {
+    int x0, y0, cols, rows;
+    gi_temporal_frame cur, hist;
+    gi_temporal_out out;
+};
+hipError_t launch_temporal(const CamDev& cam, const CamDev& prev, const TpIO& io, const gi_temporal_params& p, hipStream_t stream);
 
 }  // namespace gi

@@ -24,6 +24,8 @@
  *                        gi_occluded*
  *   gi_denoise*          an edge-avoiding a-trous filter of a frame over those feature buffers: a preview of
  *                        the first progressive passes (no reference counterpart)
+ *   gi_temporal*         reprojects the previous frame's accumulated colour and variance onto a frame's first
+ *                        hits and blends them with it: samples kept while the camera moves (no reference counterpart)
  *   gi_unshard_device    reassembles a frame from per-rank packed tiles after the RCCL gather
  *   gi_scene_kernel_ms   HIP-event duration of the last timed render's dominant kernel (bench)
  *   gi_scene_x_form      which Mode X form (persistent kernel / wavefront) a render would run
@@ -56,7 +58,7 @@
 extern "C" {
 #endif
 
-#define GI_ABI_VERSION 19
+#define GI_ABI_VERSION 20
 
 typedef enum gi_status {
     GI_OK = 0,
@@ -417,8 +419,8 @@ int gi_camera_rays(const gi_camera* cam, const gi_aov_frame* frame, double* rays
  *              gi_denoise_scratch_bytes, a NULL or not 16-byte aligned device scratch.  An empty window
  *              launches nothing and returns GI_OK.  gi_denoise_scratch_bytes (host only, no device): the
  *              bytes, or a negative gi_status for a bad frame or parameters (0 for an empty window).
- * Not provided: temporal accumulation, albedo demodulation, Mode R frames, shard-packed buffers / gi_multi
- * (a per-pixel colour stop from the samples' variance: gi_denoise_var* below). */
+ * Not provided: albedo demodulation, Mode R frames, shard-packed buffers / gi_multi (a per-pixel colour stop
+ * from the samples' variance: gi_denoise_var* below; accumulation over frames: gi_temporal* below). */
 #define GI_DENOISE_ALBEDO_STOP 1u  /* a tap contributes only if its albedo equals the centre's (three fp64 ==) */
 typedef struct gi_denoise_params {
     int32_t levels;           /* 1..8 a-trous levels, level i has step 2^i */
@@ -498,7 +500,8 @@ int gi_frame_moments(gi_scene* scene, const gi_aov_frame* frame, const gi_moment
  * denoiser".  The _device and host forms, the scratch and the argument rules are gi_denoise's, with sigma_v in
  * sigma_c's place: GI_ERR_ARG also for a var_floor that is not finite and > 0, a NULL var, all three outputs
  * NULL, out_rgb equal to rgb or out_var equal to var.
- * Not provided: temporal accumulation, albedo demodulation, Mode R frames, shard-packed buffers / gi_multi. */
+ * Not provided: albedo demodulation, Mode R frames, shard-packed buffers / gi_multi (accumulation over frames:
+ * gi_temporal* below). */
 typedef struct gi_denoise_var_params {
     int32_t levels;           /* 1..8 */
     int32_t normal_pow_log2;  /* 0..7 */
@@ -523,6 +526,93 @@ int gi_denoise_var_device(const gi_camera* cam, const gi_aov_frame* frame, const
                           const gi_denoise_var_io* d_io, void* d_scratch, int64_t scratch_bytes, void* stream);
 int gi_denoise_var(const gi_camera* cam, const gi_aov_frame* frame, const gi_denoise_var_params* p,
                    const gi_denoise_var_io* io);
+
+/* ---- temporal accumulation: reproject the previous frame's history (ABI 20) --------------------------
+ * More samples per pixel for a viewer whose camera moves over a static scene: the temporal stage of SVGF
+ * (reproject, test, blend).  The previous frame's accumulated colour and variance are reprojected onto the
+ * current frame's first hits and blended with the current frame (gi_moments.mean / var, or the frame).  No
+ * scene, no state and no scratch: like gi_denoise* and gi_camera_rays* the calls run on the current HIP device;
+ * the caller owns two sets of history planes (rgb, var, t, normal, prim, len) and swaps them each frame -- this
+ * frame's outputs and its own t, normal and prim are the next frame's history.  `frame` is the window
+ * [x0, x1) x [y0, y1) of the current w x h frame; the history planes cover the same window of the previous
+ * frame, which has the same w and h.  All planes are row-major over the window, as gi_render_aov lays them
+ * out.  d_hist == NULL (prev_cam may then be NULL) is the first frame: every valid pixel resets.
+ *
+ * The operation, exactly.  Everything is fp64, no operation is contracted, dots are summed as
+ * (x x' + y y') + z z', every component of a cross product a x b is one subtraction of two products
+ * (a.y b.z - b.y a.z, a.z b.x - b.z a.x, a.x b.y - b.x a.y).  c = cur.rgb_p, V = cur.var_p.  Per pixel p at
+ * absolute pixel (x, y):
+ *   invalid (t_p not < +inf):  out.rgb = c, out.var = V, out.len = 0.
+ *   the point seen    d_p = normalize(primary_dir(cam, x, y)),  P = cam.pos + t_p d_p  (gi_denoise's P_p).
+ *   where the previous camera saw it    with the previous camera's frame vectors as the renders make them for
+ *       a frame of width w (left, up, top_left and the pixel pitches rx, ry; primary_dir(prev, x', y') =
+ *       (top_left - (left x') rx) - (up y') ry):
+ *       A = left rx,  B = up ry,  T = top_left,  N = A x B,  det = T . N,  v = P - prev.pos,  den = v . N,
+ *       x' = -(v . (B x T)) / den,   y' = -(v . (T x A)) / den
+ *       -- the inverse of primary_dir for any basis (up need not be orthogonal to forward).
+ *   history exists only if  den det > 0  (the point lies in front of the previous camera),  x' and y' are
+ *       finite, and fx = floor(x'), fy = floor(y') satisfy x0-1 <= fx <= x1-1 and y0-1 <= fy <= y1-1, compared
+ *       as doubles before any conversion to an integer.
+ *   four taps    wx = x' - fx,  wy = y' - fy;  sum_b = 0, sum_c = sum_V = (0, 0, 0), len_h = INT32_MAX;
+ *       for j = 0, 1 (outer), i = 0, 1 (inner), sums sequential in this order:
+ *       q = (fx + i, fy + j),  b = (i ? wx : 1 - wx) (j ? wy : 1 - wy);  the tap is skipped unless all of
+ *           b > 0;  q inside the window;  hist.t_q < +inf;  hist.len_q >= 1;
+ *           (GI_TEMPORAL_PRIM_STOP) hist.prim_q == cur.prim_p;
+ *           n_p . n_q >= cos_min;
+ *           |n_p . (P_q - P)| <= sigma_p t_p,  P_q = prev.pos + hist.t_q normalize(primary_dir(prev, q))
+ *       hold (a NaN in a comparison skips the tap);  an accepted tap adds
+ *           sum_b += b;  sum_c += b hist.rgb_q;  sum_V += b hist.var_q;  len_h = min(len_h, hist.len_q).
+ *       The variance is interpolated linearly, as if the four taps were fully correlated: deliberately
+ *       conservative (independent taps would give the smaller sum b^2 V_q / sum_b^2).
+ *   blend    no accepted tap (or no history): the pixel resets, out.rgb = c, out.var = V, out.len = 1.
+ *       Otherwise h_c = sum_c / sum_b,  h_V = sum_V / sum_b,  out.len = min(len_h + 1, max_history) (formed
+ *       without overflow),  a = max(1 / (double)out.len, alpha_min)  (u > v ? u : v),
+ *       out.rgb = ((1 - a) h_c) + (a c),   out.var = (((1 - a) (1 - a)) h_V) + ((a a) V).
+ * Nothing is clamped (gi_denoise* clamps at the end).  Up to max_history samples the result is the running
+ * mean of the reprojected frames, after that an exponential window.  No transcendental function appears: a
+ * restatement with the same order is exact (tests/temporal_ref.py).
+ *
+ * The caller's planes are trusted as in gi_denoise: garbage values give unspecified pixels, never a fault;
+ * hist.len and the prim planes are only compared and min'ed, never used as an index.
+ * The _device form takes device pointers and is asynchronous on `stream` (hipStream_t; NULL = default
+ * stream): it makes no allocation, no copy and no host synchronisation.  gi_temporal does the same from /
+ * into host buffers (stage, launch, copy back) and is synchronous.
+ *   Outputs    any pointer of gi_temporal_out may be NULL and is then not written.
+ *   Arguments  GI_ERR_ARG for a NULL cam, frame, p, cur or out; a NULL prev_cam with a history; a NULL cur.rgb,
+ *              cur.t or cur.normal; a NULL hist.rgb, hist.t, hist.normal or hist.len in a history; a NULL prim
+ *              on either side with GI_TEMPORAL_PRIM_STOP; out.var set while cur.var is NULL, or while a history
+ *              is given and hist.var is NULL; all three outputs NULL; an output pointer equal to a pointer of cur
+ *              or hist (the taps gather: in place is not allowed); max_history < 1, alpha_min outside [0, 1],
+ *              cos_min outside [-1, 1], a sigma_p that is not > 0 (+inf is allowed), a NaN in any of them, an
+ *              unknown flag; a bad frame or window and a camera (either one) with a non-finite field, as
+ *              gi_render_aov judges them.  An empty window launches nothing and returns GI_OK.
+ * Defaults and what they do on the Cornell box: README.md "Temporal accumulation".
+ * Not provided: albedo demodulation, a spatial variance estimate for short histories, motion of the scene itself
+ * (static scenes: the camera moves), Mode R frames, shard-packed buffers / gi_multi, the C++ drop-in headers, an
+ * RGB888 output (run gi_denoise* or quantise the plane). */
+#define GI_TEMPORAL_PRIM_STOP 1u   /* a history tap counts only if its prim equals the pixel's */
+typedef struct gi_temporal_params {
+    int32_t max_history;   /* >= 1: out_len saturates here (an exponential window after that) */
+    uint32_t flags;        /* GI_TEMPORAL_* */
+    double alpha_min;      /* in [0, 1]: lower bound of the blend weight of the current frame */
+    double cos_min;        /* in [-1, 1]: a tap needs n_p . n_q >= cos_min */
+    double sigma_p;        /* > 0, +inf = no plane stop; plane distance in units of the pixel's t (gi_denoise's) */
+} gi_temporal_params;
+typedef struct gi_temporal_frame {      /* planes over the window, gi_render_aov's layout */
+    const double* rgb;     /* rows*cols*3  cur: this frame (gi_moments.mean or the frame); hist: accumulated colour */
+    const double* var;     /* rows*cols*3  variance of the mean; NULL in cur = no variance is carried */
+    const double* t;       /* rows*cols    gi_aov.t; valid iff t < +inf */
+    const double* normal;  /* rows*cols*3  gi_aov.normal */
+    const int32_t* prim;   /* rows*cols    gi_aov.prim; may be NULL without GI_TEMPORAL_PRIM_STOP */
+    const int32_t* len;    /* rows*cols    hist only: samples accumulated per pixel (0 = none); ignored in cur */
+} gi_temporal_frame;
+typedef struct gi_temporal_out { double* rgb; double* var; int32_t* len; } gi_temporal_out;
+int gi_temporal_device(const gi_camera* cam, const gi_camera* prev_cam, const gi_aov_frame* frame,
+                       const gi_temporal_params* p, const gi_temporal_frame* d_cur, const gi_temporal_frame* d_hist,
+                       const gi_temporal_out* d_out, void* stream);
+int gi_temporal(const gi_camera* cam, const gi_camera* prev_cam, const gi_aov_frame* frame,
+                const gi_temporal_params* p, const gi_temporal_frame* cur, const gi_temporal_frame* hist,
+                const gi_temporal_out* out);
 
 /* Average duration in ms of the dominant kernel over the scene's renders issued with GI_FLAG_TIME
  * since the previous call (waits for the last one; *n = how many, may be NULL), then resets.
