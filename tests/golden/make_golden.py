@@ -11,6 +11,9 @@ Fixtures are data only (inputs and the reference's outputs):
   tree_<scene>.json     octree statistics + sha256 of the `tree` dump (octree.h structure)
   rays_<scene>.npz      per-(ray, entity) intersect/getTextureCoord KAT on seeded random rays
   boxes.npz             ExpBox node-test KAT (entities.h:379-440) on seeded random boxes/rays
+  rcam_<scene>.npz      (`cameras`) whole 40 x 28 Mode R frames from the camera placements of
+                        tests/r_cameras.py, stacked per scene: per placement its pos, look-at, focal, w, h and
+                        the reference's rgb / hit / uv / ncand / nnode / q
 """
 from __future__ import annotations
 
@@ -195,9 +198,38 @@ def make_whole_frames(jobs: int = 8, band: int = 8):
         print("whole", scene, w, h, d["rgb8_sha256"], int(sum(d["row_nan"])), "NaN pixels")
 
 
+# Mode R away from the default camera: tests/r_cameras.py's placements, every pixel of each 40 x 28 frame
+# through the compiled reference, one file per scene.  A file that would not stay smaller than the largest
+# fixture of the other kinds is not written (the host test's live comparison covers its scene).
+def make_cameras():
+    import r_cameras as RC
+    limit = max(os.path.getsize(os.path.join(HERE, f)) for f in os.listdir(HERE) if not f.startswith("rcam_"))
+    keys = ("rgb", "hit", "uv", "ncand", "nnode", "q")
+    for scene in RC.SCENES:
+        cols = {k: [] for k in ("pos", "look", "focal", "w", "h") + keys}
+        for name, pos, look, focal in RC.CAMERAS[scene]:
+            r = U.ref_render(RC.scene_at(scene, name).to_scn(), RC.W, RC.H)
+            idx = np.arange(RC.W * RC.H)
+            assert (r["x"] == idx % RC.W).all() and (r["y"] == idx // RC.W).all()   # the whole frame, row-major
+            for k, v in (("pos", pos), ("look", look), ("focal", focal), ("w", RC.W), ("h", RC.H)):
+                cols[k].append(v)
+            for k in keys:
+                cols[k].append(r[k])
+        path = RC.golden_path(scene)
+        meta = dict(scene=scene, placements=[p[0] for p in RC.CAMERAS[scene]], scene_sha256=RC.base_scene(scene).digest())
+        np.savez_compressed(path, meta=np.array(json.dumps(meta)), **{k: np.array(v) for k, v in cols.items()})
+        size = os.path.getsize(path)
+        if size >= limit:
+            os.remove(path)
+        print("cameras", scene, len(meta["placements"]), "frames,", size, "bytes" + (" (over the limit: not kept)" if size >= limit else ""))
+
+
 if __name__ == "__main__":
     if not U.have_ref():
         sys.exit("oracle/_ref/ref_harness missing: run `make -C oracle ref` where /root/reference exists")
+    if sys.argv[1:] == ["cameras"]:   # the camera placements' frames only
+        make_cameras()
+        sys.exit(0)
     if sys.argv[1:] == ["whole"]:   # the whole 1080p Mode R frames only (minutes over 8 processes)
         make_whole_frames()
         sys.exit(0)
