@@ -52,6 +52,7 @@ __all__ = [
     "denoise_var", "denoise_var_scratch_bytes", "denoise_var_device",
     "TemporalParams", "TemporalFrame", "TemporalOut", "TEMPORAL_PRIM_STOP", "TEMPORAL_OUTPUTS", "TEMPORAL_PLANES",
     "temporal", "temporal_device",
+    "AdaptiveParams", "AdaptiveOut", "ADAPTIVE_RELATIVE", "ADAPTIVE_OUTPUTS",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -78,7 +79,7 @@ STAT_X_IT_RS, STAT_X_LN_RS, STAT_X_IT_ST, STAT_X_LN_ST = 20, 21, 22, 23
 STAT_R_PAIRS, STAT_R_OVF_TILES = 24, 25
 STATS_N = 26
 TILE = 8
-ABI_VERSION = 20
+ABI_VERSION = 21
 RAY_DOUBLES = 8   # a ray record of the batched queries: o[3], d[3], tmax, reserved (gi.h GI_RAY_DOUBLES)
 # the feature buffers of DeviceScene.render_aov (gi.h gi_aov, in its field order): name -> (dtype, trailing shape)
 AOV_OUTPUTS = ("t", "normal", "albedo", "prim", "entity", "uv")
@@ -195,6 +196,22 @@ class TemporalOut(ctypes.Structure):
     _fields_ = [("rgb", ctypes.c_void_p), ("var", ctypes.c_void_p), ("len", ctypes.c_void_p)]
 
 
+ADAPTIVE_RELATIVE = 1   # gi.h GI_ADAPTIVE_RELATIVE
+ADAPTIVE_OUTPUTS = ("rgb", "rgb8", "mean", "var", "n")   # gi.h gi_adaptive_out, in its field order
+_ADAPTIVE_KINDS = {"rgb": (np.float64, (3,)), "rgb8": (np.uint8, (3,)), "mean": (np.float64, (3,)),
+                   "var": (np.float64, (3,)), "n": (np.int32, ())}
+
+
+class AdaptiveParams(ctypes.Structure):
+    _fields_ = [("min_samples", ctypes.c_int32), ("flags", ctypes.c_uint32), ("tol", ctypes.c_double),
+                ("y_floor", ctypes.c_double)]
+
+
+class AdaptiveOut(ctypes.Structure):
+    _fields_ = [("rgb", ctypes.c_void_p), ("rgb8", ctypes.c_void_p), ("mean", ctypes.c_void_p), ("var", ctypes.c_void_p),
+                ("n", ctypes.c_void_p)]
+
+
 TILE_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint8),
                            ctypes.POINTER(ctypes.c_double))
 
@@ -207,7 +224,8 @@ EXPORTS = ["gi_abi_version", "gi_last_error", "gi_camera_init", "gi_scene_create
            "gi_denoise_scratch_bytes", "gi_denoise_device", "gi_denoise",
            "gi_frame_samples_info", "gi_frame_moments_device", "gi_frame_moments",
            "gi_denoise_var_scratch_bytes", "gi_denoise_var_device", "gi_denoise_var",
-           "gi_temporal_device", "gi_temporal"]
+           "gi_temporal_device", "gi_temporal",
+           "gi_render_adaptive_device", "gi_render_adaptive", "gi_adaptive_info"]
 
 _lib = None
 _lock = threading.Lock()
@@ -275,6 +293,11 @@ def lib():
                    ctypes.POINTER(TemporalFrame), ctypes.POINTER(TemporalFrame), ctypes.POINTER(TemporalOut)]
         L.gi_temporal_device.argtypes = tp_args + [vp]
         L.gi_temporal.argtypes = tp_args
+        ad_args = [vp, ctypes.POINTER(CameraDesc), dp, i32, i32, ctypes.POINTER(Opts), ctypes.POINTER(AdaptiveParams),
+                   ctypes.POINTER(AdaptiveOut)]
+        L.gi_render_adaptive_device.argtypes = ad_args + [vp]
+        L.gi_render_adaptive.argtypes = ad_args
+        L.gi_adaptive_info.argtypes = [vp, ip, ip, ip, ctypes.POINTER(ctypes.c_int64)]
         L.gi_scene_kernel_ms.argtypes =[vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)]
         L.gi_scene_x_form.argtypes = [vp, ctypes.POINTER(Opts), ctypes.POINTER(ctypes.c_int32)]
         L.gi_scene_seg_ring.argtypes = [vp, ctypes.POINTER(Opts), ctypes.POINTER(ctypes.c_int32)]
@@ -799,6 +822,52 @@ class DeviceScene:
         f = _aov_frame(w, h, window)
         m = Moments(d_mean or None, d_var or None, d_samples or None)
         _check(lib().gi_frame_moments_device(self._h, ctypes.byref(f), ctypes.byref(m), stream or None), "gi_frame_moments_device")
+
+    # ---- adaptive sampling (gi.h "adaptive sampling") --------------------------------------------------
+    @staticmethod
+    def _adaptive_params(min_samples, tol, relative, y_floor) -> AdaptiveParams:
+        return AdaptiveParams(min_samples, ADAPTIVE_RELATIVE if relative else 0, tol, y_floor)
+
+    def render_adaptive(self, cam: Camera, light, w: int, h: int, samples, spp: int, depth: int = 1, seed=0, tol: float = 0.01,
+                        min_samples: int = 4, relative: bool = False, y_floor: float = 0.0, flags=0, stats_ptr=0,
+                        want=("rgb", "n")) -> dict:
+        """One pass, Mode X samples [begin, end) = samples, of an adaptive frame of at most spp samples per pixel
+        (gi_render_adaptive): traces the pixels still active, then stops those whose variance of the mean, summed
+        over the channels, is at most tol^2 (relative: (tol max(r + g + b, y_floor))^2) once they have min_samples.
+        Returns the planes named in want, over the whole frame: "rgb" (h, w, 3) float64 and "rgb8" uint8, the
+        delivered frame; "mean" and "var" (h, w, 3), the unclamped mean and the one-pass variance of the mean;
+        "n" (h, w) int32, the samples each pixel has received.  ValueError for an unknown, repeated or empty want."""
+        want = tuple(want)
+        if not want or any(k not in ADAPTIVE_OUTPUTS for k in want) or len(set(want)) != len(want):
+            raise ValueError(f"render_adaptive: want is a non-empty selection of {ADAPTIVE_OUTPUTS}")
+        bufs = {k: np.empty((h, w) + _ADAPTIVE_KINDS[k][1], _ADAPTIVE_KINDS[k][0]) for k in want}
+        o = self.opts(MODE_X, spp, depth, seed, stats_ptr=stats_ptr, flags=flags, samples=samples)
+        p = self._adaptive_params(min_samples, tol, relative, y_floor)
+        a = AdaptiveOut(**{k: bufs[k].ctypes.data for k in want})
+        _check(lib().gi_render_adaptive(self._h, ctypes.byref(cam._c), _d3(light), w, h, ctypes.byref(o), ctypes.byref(p),
+                                        ctypes.byref(a)), "gi_render_adaptive")
+        return bufs
+
+    def render_adaptive_device(self, cam: Camera, light, w: int, h: int, samples, spp: int, depth: int = 1, seed=0,
+                               tol: float = 0.01, min_samples: int = 4, relative: bool = False, y_floor: float = 0.0, flags=0,
+                               stats_ptr=0, d_rgb: int = 0, d_rgb8: int = 0, d_mean: int = 0, d_var: int = 0, d_n: int = 0,
+                               stream: int = 0) -> None:
+        """Asynchronous render_adaptive into device planes (gi_render_adaptive_device): no allocation per call beyond
+        the scene's scratch, no copy, no host synchronisation -- a schedule of passes can be queued without reading
+        anything back; pointers are ints, an output of 0 is not written."""
+        o = self.opts(MODE_X, spp, depth, seed, stats_ptr=stats_ptr, flags=flags, samples=samples)
+        p = self._adaptive_params(min_samples, tol, relative, y_floor)
+        a = AdaptiveOut(d_rgb or None, d_rgb8 or None, d_mean or None, d_var or None, d_n or None)
+        _check(lib().gi_render_adaptive_device(self._h, ctypes.byref(cam._c), _d3(light), w, h, ctypes.byref(o),
+                                               ctypes.byref(p), ctypes.byref(a), stream or None), "gi_render_adaptive_device")
+
+    def adaptive_info(self) -> dict:
+        """The adaptive frame: {"w", "h", "samples_done" (the last pass's end), "active" (pixels still traced)}
+        (gi_adaptive_info: waits for the last pass); GIError without one."""
+        v = [ctypes.c_int32() for _ in range(3)]
+        act = ctypes.c_int64()
+        _check(lib().gi_adaptive_info(self._h, *(ctypes.byref(x) for x in v), ctypes.byref(act)), "gi_adaptive_info")
+        return {"w": int(v[0].value), "h": int(v[1].value), "samples_done": int(v[2].value), "active": int(act.value)}
 
     def kat_x_variant(self, flags: int = 0) -> dict:
         """The kernel variant kat_x_query runs with these flags (flags 0: k_seg's for this scene):

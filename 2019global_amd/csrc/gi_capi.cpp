@@ -56,6 +56,12 @@ struct gi_scene {
     // rows' stride and its camera (k_x_moments_fill repeats the classify pass's test)
     int keep_w = 0, keep_h = 0, keep_n = 0, keep_spp = 0;
     CamDev keep_cam;
+    // the adaptive frame (gi.h "adaptive sampling"): its key (prog_key's, with the gi_adaptive_params), the next
+    // pass's sample_begin (-1: no pass can continue it), which of the two lists that pass reads, and what
+    // gi_adaptive_info reports (ad_done 0: no adaptive frame).  Any other render of the scene ends it.
+    uint64_t ad_key = 0;
+    int ad_next = -1, ad_cur = 0;
+    int ad_w = 0, ad_h = 0, ad_done = 0;
     std::mutex mu;     // host-side calls on one scene are serialised
     int device = -1;
     int64_t bytes = 0;
@@ -317,6 +323,10 @@ void destroy_scene(gi_scene* s) noexcept {
         (void)hipFree(s->xs.wid[q]);
     }
     (void)hipFree(s->xs.wcnt);
+    (void)hipFree(s->xs.ad_list);
+    (void)hipFree(s->xs.ad_cnt);
+    (void)hipFree(s->xs.ad_sum);
+    (void)hipFree(s->xs.ad_n);
     free_rflat(s->xs);
     for (int i = 0; i < KTimer::kRing; i++) {
         if (s->kt.ev0[i]) (void)hipEventDestroy(static_cast<hipEvent_t>(s->kt.ev0[i]));
@@ -566,6 +576,8 @@ std::mutex& scene_mutex(gi_scene* s) { return s->mu; }
 int scene_render_band(gi_scene* s, const CamDev& cd, const double light[3], int w, int h, int y0, const gi_opts& o,
                       double* d_rgb, uint8_t* d_rgb8, hipStream_t stream, bool timer) {
     s->keep_n = 0;   // (every render ends the retained frame; a whole frame that succeeds becomes the next one)
+    s->ad_next = -1;   // (and the adaptive frame)
+    s->ad_done = 0;
     int rc = bind_device(s->device);
     if (rc || (rc = ensure_xscratch(s, w, h, &o)) || (timer && (rc = ensure_timer(s, &o)))) return rc;
     return issue_render(s, cd, v3(light[0], light[1], light[2]), w, h, y0, o, d_rgb, d_rgb8, stream, timer);
@@ -662,6 +674,8 @@ int gi_render_device(gi_scene* s, const gi_camera* cam, const double light[3], i
         if (!s) return fail(GI_ERR_ARG, "null scene");
         std::lock_guard<std::mutex> lk(s->mu);
         s->keep_n = 0;   // (a refused render too ends the retained frame)
+        s->ad_next = -1;   // (and the adaptive frame)
+        s->ad_done = 0;
         int rc = check_opts(w, h, o);
         if (rc) return rc;
         if (!cam || !light) return fail(GI_ERR_ARG, "null camera or light");
@@ -683,6 +697,8 @@ int gi_render(gi_scene* s, const gi_camera* cam, const double light[3], int w, i
         if (!s) return fail(GI_ERR_ARG, "null scene");
         std::lock_guard<std::mutex> lk(s->mu);
         s->keep_n = 0;   // (a refused render too ends the retained frame)
+        s->ad_next = -1;   // (and the adaptive frame)
+        s->ad_done = 0;
         int rc = check_opts(w, h, o);
         if (rc) return rc;
         if (!cam || !light) return fail(GI_ERR_ARG, "null camera or light");
@@ -1146,6 +1162,171 @@ int gi_frame_moments(gi_scene* s, const gi_aov_frame* frame, const gi_moments* o
         if (e == hipSuccess && out->var) e = hipMemcpy(out->var, dv.p, m * 3 * sizeof(double), hipMemcpyDeviceToHost);
         if (e == hipSuccess && out->samples) e = hipMemcpy(out->samples, ds.p, ns * sizeof(double), hipMemcpyDeviceToHost);
         return e == hipSuccess ? GI_OK : hip_fail(e, "gi_frame_moments");
+    });
+}
+
+// ---- adaptive sampling (gi.h "adaptive sampling"; gi_adapt.hip, gi_kernels.hip launch_adaptive) ----
+// A pass is a render: under the scene's mutex, ordered on the device by the scene's `last` event, and it ends the
+// retained frame and any plain progressive frame.  The frame's continuation state is the scene's ad_* fields.
+namespace {
+int check_adaptive(int w, int h, const gi_opts* o, const gi_adaptive_params* p, const gi_adaptive_out* out) {
+    int rc = check_opts(w, h, o);
+    if (rc) return rc;
+    if (!p || !out) return fail(GI_ERR_ARG, "gi_render_adaptive: null params or output struct");
+    if (!out->rgb && !out->rgb8 && !out->mean && !out->var && !out->n) return fail(GI_ERR_ARG, "gi_render_adaptive: every output is null");
+    if (o->mode != GI_MODE_X) return fail(GI_ERR_ARG, "gi_render_adaptive: mode X only");
+    if (o->shard_count != 1) return fail(GI_ERR_ARG, "gi_render_adaptive: whole frames only (shard_count 1)");
+    if (o->sample_begin < 0 || o->sample_end > o->spp || (int64_t)o->sample_end - (int64_t)o->sample_begin < 2)
+        return fail(GI_ERR_ARG, "gi_render_adaptive: a pass is 0 <= sample_begin, sample_begin + 2 <= sample_end <= spp");
+    if (p->min_samples < 2) return fail(GI_ERR_ARG, "gi_render_adaptive: min_samples >= 2");
+    if (p->flags & ~GI_ADAPTIVE_RELATIVE) return fail(GI_ERR_ARG, "gi_render_adaptive: unknown flag");
+    if (!(p->tol > 0)) return fail(GI_ERR_ARG, "gi_render_adaptive: tol > 0 (+inf allowed)");
+    if ((p->flags & GI_ADAPTIVE_RELATIVE) && !(p->y_floor > 0 && std::isfinite(p->y_floor)))
+        return fail(GI_ERR_ARG, "gi_render_adaptive: GI_ADAPTIVE_RELATIVE needs a finite y_floor > 0");
+    return GI_OK;
+}
+uint64_t adaptive_key(const gi_camera& c, const double light[3], int w, int h, const gi_opts& o, const gi_adaptive_params& p) {
+    uint64_t k = prog_key(c, light, w, h, o);
+    auto mix = [&](const void* q, size_t n) {
+        for (size_t i = 0; i < n; ++i) k = (k ^ static_cast<const unsigned char*>(q)[i]) * 1099511628211ull;
+    };
+    const int64_t v[2] = {p.min_samples, (int64_t)p.flags};
+    const double d[2] = {p.tol, (p.flags & GI_ADAPTIVE_RELATIVE) ? p.y_floor : 0.0};
+    mix(v, sizeof v);
+    mix(d, sizeof d);
+    return k;
+}
+// the second list, the counts and the per-slot state for the slots the work list holds; grown, never shrunk
+int ensure_adaptive(gi_scene* s) {
+    XScratch& x = s->xs;
+    if (x.ad_cap >= x.cap && x.ad_cap > 0) return GI_OK;
+    for (void* q : {(void*)x.ad_list, (void*)x.ad_cnt, (void*)x.ad_sum, (void*)x.ad_n}) (void)hipFree(q);
+    x.ad_list = x.ad_cnt = nullptr;
+    x.ad_sum = nullptr;
+    x.ad_n = nullptr;
+    x.ad_cap = 0;
+    hipError_t e;
+    if ((e = hipMalloc((void**)&x.ad_list, (size_t)x.cap * sizeof(unsigned))) != hipSuccess ||
+        (e = hipMalloc((void**)&x.ad_cnt, 4 * sizeof(unsigned))) != hipSuccess ||
+        (e = hipMalloc((void**)&x.ad_sum, (size_t)x.cap * 6 * sizeof(double))) != hipSuccess ||
+        (e = hipMalloc((void**)&x.ad_n, (size_t)x.cap * sizeof(int32_t))) != hipSuccess)
+        return hip_fail(e, "hipMalloc (adaptive state)");
+    x.ad_cap = x.cap;
+    return GI_OK;
+}
+// one pass with device planes on `stream`; the scene's mutex is held
+int adaptive_pass(gi_scene* s, const gi_camera* cam, const double light[3], int w, int h, const gi_opts* o,
+                  const gi_adaptive_params* p, const gi_adaptive_out* d_out, hipStream_t stream) {
+    // a render: it ends the retained frame and a plain progressive frame; a refused pass ends the adaptive frame too
+    const int next = s->ad_next;
+    s->keep_n = 0;
+    s->prog_next = -1;
+    s->ad_next = -1;
+    if (!cam || !light) return fail(GI_ERR_ARG, "null camera or light");
+    int rc = check_adaptive(w, h, o, p, d_out);
+    if (rc) return rc;
+    const uint64_t key = adaptive_key(*cam, light, w, h, *o, *p);
+    if (o->sample_begin > 0) {
+        if (next != o->sample_begin || s->ad_key != key || !s->launched)
+            return fail(GI_ERR_ARG, "adaptive pass out of order: a pass continues the previous adaptive pass's frame (same camera, "
+                                    "light, size, spp, depth, seed, flags and params) from its sample_end");
+        // the previous pass was accepted when issued: a device error since ends the frame
+        const hipError_t q = hipEventQuery(s->last);
+        if (q != hipSuccess && q != hipErrorNotReady)
+            return hip_fail(q, "adaptive pass: the previous pass failed on the device; restart the frame at sample 0");
+    }
+    gi_opts o2 = *o;   // the pass as the render kernels see it: the stride of its rows is its k samples
+    o2.spp = o->sample_end - o->sample_begin;
+    if ((rc = bind_device(s->device)) || (rc = ensure_xscratch(s, w, h, &o2)) || (rc = ensure_adaptive(s)) || (rc = ensure_timer(s, &o2)))
+        return rc;
+    const CamDev cd = make_cam(*cam, w);
+    XAdaptPass ap;
+    ap.p = *p;
+    ap.out = *d_out;
+    ap.spp_max = o->spp;
+    ap.cur = o->sample_begin > 0 ? s->ad_cur : 0;
+    hipError_t e = hipSuccess;
+    if (!s->last && (e = hipEventCreateWithFlags(&s->last, hipEventDisableTiming)) != hipSuccess) return hip_fail(e, "hipEventCreate");
+    if (s->launched && (e = hipStreamWaitEvent(stream, s->last, 0)) != hipSuccess) return hip_fail(e, "hipStreamWaitEvent");
+    s->ad_done = 0;
+    e = launch_adaptive(s->dev, s->xcfg, cd, v3(light[0], light[1], light[2]), w, h, o2, ap, s->xs, &s->kt, stream);
+    if (e != hipSuccess) return hip_fail(e, "adaptive pass launch");
+    if ((e = hipEventRecord(s->last, stream)) != hipSuccess) return hip_fail(e, "hipEventRecord");
+    s->launched = true;
+    s->ad_key = key;
+    s->ad_cur = ap.cur ^ 1;   // the survivors' list: the next pass's, and the count gi_adaptive_info reads
+    s->ad_next = o->sample_end < o->spp ? o->sample_end : -1;
+    s->ad_w = w;
+    s->ad_h = h;
+    s->ad_done = o->sample_end;
+    return GI_OK;
+}
+}  // namespace
+
+int gi_render_adaptive_device(gi_scene* s, const gi_camera* cam, const double light[3], int w, int h, const gi_opts* o,
+                              const gi_adaptive_params* p, const gi_adaptive_out* d_out, void* stream) {
+    return guard([&]() -> int {
+        DeviceRestore keep;   // the caller's current device, restored on return
+        if (!s) return fail(GI_ERR_ARG, "null scene");
+        std::lock_guard<std::mutex> lk(s->mu);
+        return adaptive_pass(s, cam, light, w, h, o, p, d_out, static_cast<hipStream_t>(stream));
+    });
+}
+
+int gi_render_adaptive(gi_scene* s, const gi_camera* cam, const double light[3], int w, int h, const gi_opts* o,
+                       const gi_adaptive_params* p, const gi_adaptive_out* out) {
+    return guard([&]() -> int {
+        DeviceRestore keep;   // the caller's current device, restored on return
+        if (!s) return fail(GI_ERR_ARG, "null scene");
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (!out || w <= 0 || h <= 0 || (int64_t)w * h > (int64_t)1 << 34)   // (the rest: adaptive_pass)
+            return adaptive_pass(s, cam, light, w, h, o, p, out, nullptr);
+        int rc = bind_device(s->device);
+        if (rc) return rc;
+        const size_t px = (size_t)w * (size_t)h;
+        DevBuf b_rgb, b_rgb8, b_mean, b_var, b_n;
+        hipError_t e = hipSuccess;
+        if (out->rgb) e = b_rgb.alloc(px * 3 * sizeof(double));
+        if (e == hipSuccess && out->rgb8) e = b_rgb8.alloc(px * 3);
+        if (e == hipSuccess && out->mean) e = b_mean.alloc(px * 3 * sizeof(double));
+        if (e == hipSuccess && out->var) e = b_var.alloc(px * 3 * sizeof(double));
+        if (e == hipSuccess && out->n) e = b_n.alloc(px * sizeof(int32_t));
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc (adaptive staging)");
+        const gi_adaptive_out d{static_cast<double*>(b_rgb.p), static_cast<uint8_t*>(b_rgb8.p), static_cast<double*>(b_mean.p),
+                                static_cast<double*>(b_var.p), static_cast<int32_t*>(b_n.p)};
+        if ((rc = adaptive_pass(s, cam, light, w, h, o, p, &d, nullptr))) return rc;
+        if (out->rgb) e = hipMemcpy(out->rgb, d.rgb, px * 3 * sizeof(double), hipMemcpyDeviceToHost);   // (synchronous copies on the launch's stream)
+        if (e == hipSuccess && out->rgb8) e = hipMemcpy(out->rgb8, d.rgb8, px * 3, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && out->mean) e = hipMemcpy(out->mean, d.mean, px * 3 * sizeof(double), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && out->var) e = hipMemcpy(out->var, d.var, px * 3 * sizeof(double), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && out->n) e = hipMemcpy(out->n, d.n, px * sizeof(int32_t), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) {
+            s->ad_next = -1;
+            return hip_fail(e, "gi_render_adaptive");
+        }
+        return GI_OK;
+    });
+}
+
+int gi_adaptive_info(gi_scene* s, int32_t* w, int32_t* h, int32_t* samples_done, int64_t* active) {
+    return guard([&]() -> int {
+        DeviceRestore keep;   // the caller's current device, restored on return
+        if (!s) return fail(GI_ERR_ARG, "null scene");
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (s->ad_done == 0) return fail(GI_ERR_ARG, "gi_adaptive_info: no adaptive frame");
+        int rc = bind_device(s->device);
+        if (rc) return rc;
+        unsigned cnt = 0;
+        if (active) {   // waits for the last pass, then reads the survivors' count
+            hipError_t e = hipEventSynchronize(s->last);
+            if (e == hipSuccess) e = hipMemcpy(&cnt, s->xs.ad_cnt + s->ad_cur, sizeof cnt, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) return hip_fail(e, "gi_adaptive_info");
+        }
+        if (w) *w = s->ad_w;
+        if (h) *h = s->ad_h;
+        if (samples_done) *samples_done = s->ad_done;
+        if (active) *active = (int64_t)cnt;
+        return GI_OK;
     });
 }
 

@@ -1131,10 +1131,21 @@ void x_dispatch(const DevScene& sc, bool help, bool stats, F&& f) {
                stats, help, sc.xcnodes != nullptr, sc.x_max_depth <= 7, sc.x_tri_only != 0);
 }
 
-// launch_render's Mode X half: classify, the form's pass between ev_begin and ev_end, reduce
+// An adaptive pass's work as the kernels of a form take it (launch_adaptive): the list of the active pixel slots and
+// its device count in the work list's place, and the rows pointer biased by -3 s0 doubles, so that with the stride
+// o.spp = k sample s of active entry i lands at rows[i][s - s0] (only such in-bounds addresses are dereferenced).
+struct XPassWork {
+    unsigned* list;
+    unsigned* n_list;
+    double* part;
+};
+
+// launch_render's Mode X half: classify, the form's pass between ev_begin and ev_end, reduce.  pw (an adaptive pass):
+// the form's kernels run over pw's list; classify fills it on the frame's first pass and is not run on a later one
+// (no pixel is written here: rgb and rgb8 are null), and the rows are left to k_x_adapt_fold instead of k_x_reduce.
 hipError_t launch_mode_x(const DevScene& sc, const XLaunchCfg& xc, const CamDev& cam, V3 light, const TileMap& m,
                          const gi_opts& o, double* rgb, uint8_t* rgb8, const XScratch& xs, hipStream_t stream,
-                         hipEvent_t ev_begin, hipEvent_t ev_end) {
+                         hipEvent_t ev_begin, hipEvent_t ev_end, const XPassWork* pw = nullptr) {
     const dim3 block(64 * kWavesPerBlock);
     unsigned long long* st = reinterpret_cast<unsigned long long*>(o.stats);
     const bool stats = (o.flags & GI_FLAG_STATS) && st;
@@ -1160,15 +1171,21 @@ hipError_t launch_mode_x(const DevScene& sc, const XLaunchCfg& xc, const CamDev&
     hipError_t e = hipMemsetAsync(sc.work, 0, (cont ? 1 : 16) * sizeof(unsigned), stream);
     if (e == hipSuccess && cont) e = hipMemsetAsync(sc.work + 2, 0, 14 * sizeof(unsigned), stream);
     if (e != hipSuccess) return e;
-    const XWork wk{xs.list, sc.work + 1, xs.part, sc.work, s0, s1};   // (list, its count, rows, block counter, samples)
+    unsigned* const n_list = pw ? pw->n_list : sc.work + 1;
+    const XWork wk{pw ? pw->list : xs.list, n_list, pw ? pw->part : xs.part, sc.work, s0, s1};   // (list, its count, rows, block counter, samples)
     const dim3 sgrid((unsigned)((n_slots + 255) / 256));
     const dim3 cgrid((unsigned)((n_slots + kClassifyBlock - 1) / kClassifyBlock));
     const XForm form = x_form_choice(sc, xc, o);
     unsigned* zero2 = form == XFORM_SEG ? xs.wcnt : nullptr;   // k_seg's unit counter, zeroed by the classify pass
-    unsigned* cl = cont ? nullptr : xs.list;
-    with_bools([&](auto S) {
-        hipLaunchKernelGGL(k_x_classify<S.value>, cgrid, dim3(kClassifyBlock), 0, stream, sc, cam, m, s1 - s0, rgb, rgb8, cl, sc.work + 1, st, zero2);
-    }, stats);
+    unsigned* cl = cont ? nullptr : pw ? pw->list : xs.list;
+    if (pw && cont && !stats) {   // (an adaptive pass after the first: only k_seg's unit counter, which classify would zero;
+                                  //  with GI_FLAG_STATS classify runs for the resolved pixels' counts, as in a progressive pass)
+        if (zero2 && (e = hipMemsetAsync(zero2, 0, 2 * sizeof(unsigned), stream)) != hipSuccess) return e;
+    } else {
+        with_bools([&](auto S) {
+            hipLaunchKernelGGL(k_x_classify<S.value>, cgrid, dim3(kClassifyBlock), 0, stream, sc, cam, m, s1 - s0, rgb, rgb8, cl, n_list, st, zero2);
+        }, stats);
+    }
     // shading-handler threshold (eighths of the live lanes that must wait): the builder's
     // estimate for the scene (DevScene::x_handle8)
     const int h8 = sc.x_handle8;
@@ -1180,7 +1197,12 @@ hipError_t launch_mode_x(const DevScene& sc, const XLaunchCfg& xc, const CamDev&
         if (!xs.wcnt || (form == XFORM_WF && (!xs.wq[0] || !xs.wq[1] || xs.wcap <= 0))) return hipErrorInvalidValue;
         const bool seg = form == XFORM_SEG;
         const XKernelCfg c{xc.var, env.flat != 0, seg ? xc.seg_lds_bytes : xc.wf_lds_bytes, xc.wf_grid[seg ? WK_SEG : WK_BOUNCE]};
-        e = launch_wf(sc, c, form, cam, light, m.w, m.h, m.y0, o, rgb, rgb8, xs, sc.work + 1, stats ? st : nullptr, xf,
+        XScratch xw = xs;   // (gi_wf.hip's forms read the list and the rows from the scratch record)
+        if (pw) {
+            xw.list = pw->list;
+            xw.part = pw->part;
+        }
+        e = launch_wf(sc, c, form, cam, light, m.w, m.h, m.y0, o, rgb, rgb8, xw, n_list, stats ? st : nullptr, xf,
                       x_launch_live(sc, xc, cam.pos, light, o.flags), stream,
                       ev_begin, ev_end);
         if (e != hipSuccess) return e;
@@ -1192,10 +1214,41 @@ hipError_t launch_mode_x(const DevScene& sc, const XLaunchCfg& xc, const CamDev&
         });
         if (ev_end) (void)hipEventRecord(ev_end, stream);
     }
-    if (o.spp > 1) hipLaunchKernelGGL(k_x_reduce, sgrid, dim3(256), 0, stream, m, wk, o.spp, rgb, rgb8);
+    if (o.spp > 1 && !pw) hipLaunchKernelGGL(k_x_reduce, sgrid, dim3(256), 0, stream, m, wk, o.spp, rgb, rgb8);
     return hipSuccess;
 }
 }  // namespace
+
+// One adaptive pass (gi_launch.h XAdaptPass): o.spp is the pass's k.  The grids, the handoff choice, k_seg's unit
+// counter and the wavefront chunks all follow the frame's slots x k (the active count stays on the device; what lies
+// past it returns at once there), none of them the frame's spp.
+hipError_t launch_adaptive(const DevScene& sc, const XLaunchCfg& xc, const CamDev& cam, V3 light, int w, int h,
+                           const gi_opts& o, const XAdaptPass& ap, const XScratch& xs, KTimer* kt, hipStream_t stream) {
+    const int s0 = o.sample_begin, s1 = o.sample_end, k = s1 - s0;
+    const TileMap m = make_map(w, h, 1, 0);
+    const long long n_slots = m.n_local * (kTile * kTile);
+    if (o.mode != GI_MODE_X || o.shard_count != 1 || k < 2 || o.spp != k || s0 < 0 || s1 > ap.spp_max || !xs.list || !xs.part ||
+        !xs.ad_list || !xs.ad_cnt || !xs.ad_sum || !xs.ad_n || xs.cap < n_slots || xs.ad_cap < n_slots || xs.spp < k || (ap.cur & ~1))
+        return hipErrorInvalidValue;
+    const bool timed = (o.flags & GI_FLAG_TIME) && kt && kt->ev0[0];
+    const int slot = timed ? (int)(kt->recorded % KTimer::kRing) : 0;
+    hipEvent_t ev_begin = timed ? static_cast<hipEvent_t>(kt->ev0[slot]) : nullptr;
+    hipEvent_t ev_end = timed ? static_cast<hipEvent_t>(kt->ev1[slot]) : nullptr;
+    // the counts: on the first pass both are zeroed (classify counts list 0 up), later the survivors' alone
+    hipError_t e = s0 == 0 ? hipMemsetAsync(xs.ad_cnt, 0, 2 * sizeof(unsigned), stream)
+                           : hipMemsetAsync(xs.ad_cnt + (ap.cur ^ 1), 0, sizeof(unsigned), stream);
+    if (e != hipSuccess) return e;
+    if (s0 == 0 && ap.cur != 0) return hipErrorInvalidValue;
+    XPassWork pw;
+    pw.list = ap.cur ? xs.ad_list : xs.list;
+    pw.n_list = xs.ad_cnt + ap.cur;
+    pw.part = xs.part - 3 * (ptrdiff_t)s0;
+    if ((e = launch_mode_x(sc, xc, cam, light, m, o, nullptr, nullptr, xs, stream, ev_begin, ev_end, &pw)) != hipSuccess) return e;
+    if (s0 == 0 && (e = launch_adapt_init(sc, cam, w, h, xs, stream)) != hipSuccess) return e;
+    if ((e = launch_adapt_fold(w, h, s0, s1, ap, xs, stream)) != hipSuccess) return e;
+    if (timed) kt->recorded++;
+    return hipGetLastError();
+}
 
 hipError_t x_launch_config(const DevScene& sc, int device, XLaunchCfg& cfg) {
     const bool lds = sc.x_lds_bytes > 0;   // (gi_wf.hip's kernels; k_mode_x reads every scene from global memory)

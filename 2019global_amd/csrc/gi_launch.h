@@ -1,4 +1,4 @@
-// gi_launch.h — the host functions that libgi's kernel units (gi_kernels.hip, gi_mode_r.hip, gi_wf.hip, gi_denoise.hip, gi_temporal.hip)
+// gi_launch.h — the host functions that libgi's kernel units (gi_kernels.hip, gi_adapt.hip, gi_mode_r.hip, gi_wf.hip, gi_denoise.hip, gi_temporal.hip)
 // define for each other and for gi_capi.cpp.  The only place where a cross-unit function is declared: the
 // unit that defines one and the units that call it all include this header.  Host-only, no device code.
 #pragma once
@@ -60,6 +60,30 @@ struct MomentsIO {
 };
 hipError_t launch_moments(const DevScene& sc, const XScratch& xs, const CamDev& cam, int w, int h, const MomentsIO& io,
                           hipStream_t stream);
+
+// One pass of an adaptive frame (gi_render_adaptive*).  `o` is the pass as the render kernels see it: the caller's
+// gi_opts with spp = k = sample_end - sample_begin, the rows' stride of the pass (the kernels use spp as a stride and
+// as a "> 1" switch only); spp_max is the frame's own spp.  cur: which of the two ping-pong lists (0: xs.list,
+// 1: xs.ad_list) holds the pass's active pixels; its survivors are appended to the other.  The pass's launches, all
+// on `stream`: (first pass) classify into list 0 and k_x_adapt_init; the form's kernels over the active list, their
+// rows in xs.part; k_x_adapt_fill and k_x_adapt_fold (gi_adapt.hip).
+struct XAdaptPass {
+    gi_adaptive_params p;
+    gi_adaptive_out out;
+    int spp_max;
+    int cur;
+};
+hipError_t launch_adaptive(const DevScene& sc, const XLaunchCfg& xc, const CamDev& cam, V3 light, int w, int h,
+                           const gi_opts& o, const XAdaptPass& ap, const XScratch& xs, KTimer* kt, hipStream_t stream);
+
+// ---- gi_adapt.hip: k_x_adapt_init, k_x_adapt_fill, k_x_adapt_fold ----
+// The per-slot state of a frame's first pass: n = 0 and S1 = S2 = +0 for the pixels classify listed, the resolved and
+// the padding slots marked.
+hipError_t launch_adapt_init(const DevScene& sc, const CamDev& cam, int w, int h, const XScratch& xs, hipStream_t stream);
+// After the render kernels of the pass [s0, e): the planes of the pixels that were not active in it (k_x_adapt_fill),
+// then per active entry the fold of its k = e - s0 rows, the decision, its planes and the survivors' list
+// (k_x_adapt_fold).
+hipError_t launch_adapt_fold(int w, int h, int s0, int e, const XAdaptPass& ap, const XScratch& xs, hipStream_t stream);
 
 // ---- gi_mode_r.hip: the Mode R kernels, k_trace_ray, k_box_kat ----
 RKernel r_kernel_choice(const DevScene& sc, const gi_opts& o);

@@ -373,6 +373,15 @@ struct XScratch {
     size_t rf_bytes = 0;
     long long rf_failed = 0;   // pixel slots for which the allocation failed (0: none): not retried for
                                // that many or more; such frames render through k_mode_r_batch
+    // adaptive sampling (gi_adapt.hip): the second of the two ping-pong lists of active pixel slots (the first is
+    // `list`, which the classify pass fills), their two device counts (ad_cnt[q]: entries of list q) and the
+    // per-slot state -- S1[3], S2[3] (ad_sum, 6 doubles per slot) and n with its flags (ad_n) -- for ad_cap
+    // slots.  A pass's rows go to `part`, as [active index][k][3] for its k samples.
+    unsigned* ad_list = nullptr;
+    unsigned* ad_cnt = nullptr;
+    double* ad_sum = nullptr;
+    int32_t* ad_n = nullptr;
+    long long ad_cap = 0;
 };
 
 // The Mode X kernels' xflags argument: the scene's schedule flags (DevScene::x_flags) and the launch's.

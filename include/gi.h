@@ -26,6 +26,8 @@
  *                        the first progressive passes (no reference counterpart)
  *   gi_temporal*         reprojects the previous frame's accumulated colour and variance onto a frame's first
  *                        hits and blends them with it: samples kept while the camera moves (no reference counterpart)
+ *   gi_render_adaptive*  a Mode X frame in sample passes that stop tracing the pixels whose error estimate has
+ *                        fallen below a tolerance (no reference counterpart)
  *   gi_unshard_device    reassembles a frame from per-rank packed tiles after the RCCL gather
  *   gi_scene_kernel_ms   HIP-event duration of the last timed render's dominant kernel (bench)
  *   gi_scene_x_form      which Mode X form (persistent kernel / wavefront) a render would run
@@ -58,7 +60,7 @@
 extern "C" {
 #endif
 
-#define GI_ABI_VERSION 20
+#define GI_ABI_VERSION 21
 
 typedef enum gi_status {
     GI_OK = 0,
@@ -613,6 +615,72 @@ int gi_temporal_device(const gi_camera* cam, const gi_camera* prev_cam, const gi
 int gi_temporal(const gi_camera* cam, const gi_camera* prev_cam, const gi_aov_frame* frame,
                 const gi_temporal_params* p, const gi_temporal_frame* cur, const gi_temporal_frame* hist,
                 const gi_temporal_out* out);
+
+/* ---- adaptive sampling: stop converged pixels between passes (ABI 21) ------------------------------
+ * A Mode X frame rendered in sample passes, as the progressive passes of gi_opts render it, that stops tracing a
+ * pixel once the variance of its mean is small enough.  One call is one pass of one adaptive frame, driven by the
+ * gi_opts fields: mode = GI_MODE_X; spp is the frame's maximum number of samples; [sample_begin, sample_end) is this
+ * pass, with sample_end - sample_begin >= 2 and sample_end <= spp; shard_count = 1.  The continuation rules are the
+ * progressive passes' own: the first pass starts at 0 and each later pass begins where the last one ended, with the
+ * same camera, light, size, spp, depth, seed, form flags and gi_adaptive_params, and no other render of the scene in
+ * between (GI_ERR_ARG otherwise; a device error that surfaced since the previous pass: GI_ERR_DEVICE, and the frame
+ * restarts at 0).  The form flags, GI_FLAG_STATS, GI_FLAG_TIME, GI_FLAG_X_NO_SHADOW and GI_FLAG_X_ALL_LEAVES work as
+ * in a render: a pass hands the render kernels the list of the pixels still active and traces only those.
+ *
+ * The rule, exactly.  Everything is fp64, no operation is contracted.  Per pixel the state is S1[3], S2[3] (both +0
+ * before sample 0) and n.  After a pass ending at e, for every pixel that was active in it: its radiance rows x of
+ * that pass in sample order, per channel S1 = S1 + x, S2 = S2 + (x x); then n = e.  If n >= min_samples:
+ *   per channel m = S1 / n,  v = ((S2 - S1 m) / (n-1)) / n,  then v = v > 0 ? v : 0 (a NaN v stays NaN);
+ *   err = (v.r + v.g) + v.b;   thr = tol tol;
+ *   GI_ADAPTIVE_RELATIVE:  y = (m.r + m.g) + m.b,  f = y > y_floor ? y : y_floor,  thr = (tol tol) (f f).
+ * The pixel stops iff (n >= min_samples and err <= thr) or e == spp: a NaN never stops a pixel before spp.  A
+ * stopped pixel is never traced again; its S1, n and var are final.  A pixel the classify pass resolved without
+ * traversal has x = +0 throughout and stops at the first pass with e >= min_samples (or e == spp).
+ * Outputs after every pass, for every pixel of the frame (row-major w*h planes): n; mean = S1 / n; var = the v
+ * above at the pixel's n; rgb = min(mean, 1) (mean < 1 ? mean : 1 -- as the renders) and rgb8 = quantize(rgb).  S1
+ * is the in-order sum from +0, so rgb of a pixel with n_p samples is the one-shot frame of spp = n_p at that pixel,
+ * bit for bit.  var is ONE-PASS (from S1 and S2): it is not gi_frame_moments' two-pass value, though it estimates
+ * the same quantity (equal where every operation is exact); cancellation can make S2 - S1 m slightly negative,
+ * hence the clamp at 0.
+ *
+ * gi_render_adaptive_device takes device planes and is asynchronous on `stream`: it allocates nothing per call
+ * beyond the scene's scratch grown on demand (as renders do), copies nothing and does not synchronise the host.
+ * The count of active pixels lives on the device, and a pass over an empty list is a cheap no-op that still
+ * delivers the planes: a caller may queue a fixed schedule of passes without reading anything back.
+ * gi_render_adaptive does the same into host planes (stage, one pass, copy back) and is synchronous.
+ * gi_adaptive_info is the one call that waits: it reports the adaptive frame's size, the samples issued so far (the
+ * last pass's sample_end) and the pixels still active after it (any pointer may be NULL); GI_ERR_ARG without an
+ * adaptive frame (none rendered, or another render of the scene since).
+ * Scene state: an adaptive pass is a render and is ordered like one.  It clears the retained frame
+ * (gi_frame_moments after it is GI_ERR_ARG: the rows of earlier passes are not kept).  A plain progressive pass
+ * cannot continue an adaptive frame, nor the reverse; any plain render ends the adaptive frame.  The ray queries,
+ * gi_render_aov*, the denoisers and gi_temporal* between passes do not end it.  With GI_FLAG_STATS every pass
+ * counts the resolved pixels' samples of the pass, as a progressive pass does (they cost no traversal either way);
+ * the traced rays are those of the active pixels alone.
+ *   Arguments  GI_ERR_ARG for a NULL scene, camera, light, opts, params or out struct; every plane NULL;
+ *              min_samples < 2; a tol that is NaN or <= 0 (+inf is allowed: everything stops at the first judged
+ *              pass); with GI_ADAPTIVE_RELATIVE a y_floor that is not finite and > 0; an unknown flag; a mode
+ *              other than GI_MODE_X; shard_count != 1; a pass of fewer than 2 samples or with sample_end > spp;
+ *              a pass out of order or with a changed frame, as above.
+ * Not provided: shards and gi_multi; banded gi_render; the C++ drop-in headers; passes of one sample; Mode R. */
+#define GI_ADAPTIVE_RELATIVE 1u    /* the threshold scales with the pixel's brightness: thr = (tol tol) (f f) */
+typedef struct gi_adaptive_params {
+    int32_t min_samples;   /* >= 2: no pixel is judged before it has this many */
+    uint32_t flags;        /* GI_ADAPTIVE_* */
+    double tol;            /* > 0, +inf allowed: stop when the error estimate <= tol*tol (see above) */
+    double y_floor;        /* RELATIVE only, > 0 finite */
+} gi_adaptive_params;
+typedef struct gi_adaptive_out {   /* row-major w*h planes, any may be NULL, all NULL = GI_ERR_ARG */
+    double* rgb; uint8_t* rgb8;    /* delivered frame: min(mean, 1) and its quantize() */
+    double* mean; double* var;     /* unclamped mean, variance of the mean at n */
+    int32_t* n;                    /* samples this pixel has received so far */
+} gi_adaptive_out;
+int gi_render_adaptive_device(gi_scene* scene, const gi_camera* cam, const double light[3], int w, int h,
+                              const gi_opts* opts, const gi_adaptive_params* params, const gi_adaptive_out* d_out,
+                              void* stream);
+int gi_render_adaptive(gi_scene* scene, const gi_camera* cam, const double light[3], int w, int h, const gi_opts* opts,
+                       const gi_adaptive_params* params, const gi_adaptive_out* out);
+int gi_adaptive_info(gi_scene* scene, int32_t* w, int32_t* h, int32_t* samples_done, int64_t* active);
 
 /* Average duration in ms of the dominant kernel over the scene's renders issued with GI_FLAG_TIME
  * since the previous call (waits for the last one; *n = how many, may be NULL), then resets.
