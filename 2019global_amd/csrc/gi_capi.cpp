@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -480,7 +481,20 @@ int scene_create_on(const gi_scene_desc* desc, int device, gi_scene** out) {
     std::unique_ptr<gi_scene, void (*)(gi_scene*)> s(new gi_scene(), [](gi_scene* p) { destroy_scene(p); });
     s->device = device;
     std::string err;
+    // Beyond GI_X_COORD_MAX the fp32 box tests cull boxes a ray is inside of (gi_dev.h inv_dir): no scene is
+    // made, so no render, ray query, feature buffer, adaptive pass or test hook can be asked of one.  Mode R
+    // of such a scene goes with it: its box tests clamp the reciprocal the same way.
+    auto beyond = [](double reach) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "scene coordinates reach %.9g: beyond the supported range, |coordinate| <= %.9g "
+                 "(the fp32 box tests of axis-parallel rays overflow)", reach, GI_X_COORD_MAX);
+        return fail(GI_ERR_SCENE, msg);
+    };
+    // (a triangle's vertices and a sphere's extent lie inside the structure's boxes: a scene they alone put
+    // beyond the limit is refused before anything is built; the structure's own reach decides the rest)
+    if (const double reach = x_desc_reach(*desc); !(reach <= GI_X_COORD_MAX)) return beyond(reach);
     if (!build_host_scene(*desc, s->host, err)) return fail(GI_ERR_SCENE, err);
+    if (const double reach = x_coord_reach(s->host); !(reach <= GI_X_COORD_MAX)) return beyond(reach);
     DevScene& d = s->dev;
     memset(&d, 0, sizeof d);
     const HostScene& h = s->host;

@@ -179,7 +179,23 @@ __device__ __forceinline__ double x_prim_t(const XHot& p, V3 o, V3 d, double tmi
 // for origins within the scene's extent (bounce origins; the camera of every scene here).
 // fp32 reciprocal direction (1 ulp), clamped to +-1e30 so that an axis-parallel ray gives finite
 // plane distances (fma(b, inf, -(o * inf)) would be inf - inf = NaN); with |b - o| >= the box
-// padding the clamped distances still exceed any t of the scene, so culling stays conservative
+// padding the clamped distances still exceed any t of the scene, so culling stays conservative.
+//
+// The coordinate range this holds in (GI_X_COORD_MAX, gi_scene.h; gi_scene_create refuses a scene
+// beyond it).  With C = 1e30f the clamp, a plane distance is fma(b, iv, no) with no = -(o * iv) rounded
+// on its own and |iv| <= C.  The fma rounds once, from the exact b iv + no: where that overflows, the
+// infinity has the true distance's sign and orders as the finite value would.  So only o * iv must not
+// overflow, and only where the sign of the result then misleads:
+//  * o_a outside a box's [lo_a, hi_a]: both of the box's distances on that axis become the same
+//    infinity, of the sign both true distances have -- the slab behind the ray (no hit, rightly) or
+//    ahead of it by more than any t (a hit only against tmax = inf: culls less, never more).  Far
+//    origins -- 16 extents out where tested directly (x_far_r), any distance where ray_org32 leaves
+//    them -- are of this kind on every axis on which they could overflow;
+//  * o_a inside [lo_a, hi_a]: the true distances differ in sign, one infinity for both empties the
+//    interval and culls a box the ray starts in.  Here |o_a| <= max |bound|, so o * iv is finite while
+//    max |bound| (1 + 2^-24) C <= FLT_MAX: max |bound| <= FLT_MAX / (1e30f (1 + 2^-23)) = 3.40282e8,
+//    the padding of 1e-5 extents and the outward rounding of the fp32 boxes included in the bound.
+// Beyond it axis-parallel rays that start inside the scene miss what they hit.
 __device__ __forceinline__ F3 inv_dir(V3 d) {
     return f3(__builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf((float)d.x), -1e30f, 1e30f),
               __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf((float)d.y), -1e30f, 1e30f),

@@ -244,6 +244,36 @@ struct HostScene {
 };
 // Builds every host structure of a scene from its description (gi_build.cpp); false: err says why.
 bool build_host_scene(const gi_scene_desc& desc, HostScene& hs, std::string& err);
+// The largest |bound| of a Mode X structure's fp32 boxes (padding included) the box tests are exact
+// about: FLT_MAX / (1e30f (1 + 2^-23)) = 3.40282e8, rounded down (gi_dev.h inv_dir derives it).
+// gi_scene_create refuses a scene beyond it.
+constexpr double GI_X_COORD_MAX = 3.4e8;
+// The largest |bound| of hs's fp32 child boxes: the root node's (a child's box lies inside its parent's,
+// both padded alike); 0 without a primitive.
+inline double x_coord_reach(const HostScene& hs) {
+    double m = 0.0;
+    if (!hs.xwnodes.empty())
+        for (int c = 0; c < 8; ++c)
+            if (hs.xwnodes[0].child[c] != XEMPTY)
+                for (int k = 0; k < 3; ++k)
+                    m = std::fmax(m, std::fmax(std::fabs((double)hs.xwnodes[0].lo[k][c]), std::fabs((double)hs.xwnodes[0].hi[k][c])));
+    return m;
+}
+// A lower bound of it known before the build: the largest |coordinate| of the ImpTriangles' vertices and the
+// ImpSpheres' extents (other kinds and NaNs add nothing: the built structure decides those).
+inline double x_desc_reach(const gi_scene_desc& desc) {
+    double m = 0.0;
+    for (int32_t i = 0; desc.entities && i < desc.n_entities; ++i) {
+        const gi_entity_desc& e = desc.entities[i];
+        const int n = e.kind == GI_IMP_TRIANGLE ? 9 : e.kind == GI_IMP_SPHERE ? 3 : 0;
+        const double r = e.kind == GI_IMP_SPHERE ? std::fabs(e.args[3]) : 0.0;
+        for (int k = 0; k < n; ++k) {
+            const double v = std::fabs(e.args[k]) + r;
+            if (v > m) m = v;
+        }
+    }
+    return m;
+}
 // Fills hs.xflat / x_flat_ok from hs.xwnodes (after assign_plane_groups: the group bytes are copied).
 void build_xflat(HostScene& hs);
 // Fills hs.xflat_plane / x_dead_c from xflat, the plane groups and the primitives (build_xflat calls it).

@@ -66,7 +66,7 @@ typedef enum gi_status {
     GI_OK = 0,
     GI_ERR_ARG = -1,      /* invalid argument */
     GI_ERR_DEVICE = -2,   /* HIP error / no device */
-    GI_ERR_SCENE = -3,    /* unsupported entity or material */
+    GI_ERR_SCENE = -3,    /* unsupported entity or material; coordinates beyond the supported range */
     GI_ERR_CANCELLED = -4,/* *cancel became non-zero; frame partially rendered */
     GI_ERR_NOMEM = -5,    /* host memory exhausted (std::bad_alloc inside the library) */
     GI_ERR_INTERNAL = -6  /* any other exception caught at the boundary */
@@ -254,7 +254,18 @@ const char* gi_build_id(void);
 int gi_camera_init(const double pos[3], const double look_at[3], double focal, gi_camera* out);
 
 /* Builds the reference octree and the Mode X acceleration structure on the host and uploads the
- * scene to the current HIP device (the scene is bound to that device). */
+ * scene to the current HIP device (the scene is bound to that device).
+ *
+ * Coordinate range.  Supported are scenes whose geometry, with the acceleration structure's padding of
+ * 1e-5 max(1, max |coordinate|), lies within |coordinate| <= 3.4e8 (FLT_MAX / 1e30: the kernels' fp32
+ * box tests clamp a ray's reciprocal direction to +-1e30, and beyond that range the tests of
+ * axis-parallel rays that start inside the scene overflow and cull what the rays hit).  A scene
+ * beyond it is refused here -- GI_ERR_SCENE, gi_last_error() names the limit -- so neither mode
+ * renders it and no ray query, feature buffer, adaptive pass or test hook can be asked of it.  Inside
+ * the range Mode X answers are exact at any scale and placement, and rays may start at any distance.
+ * Speed is not uniform over it: the padding grows with the distance from the world origin, not
+ * with the scene's size, so a small scene far from the origin (or one much smaller than 1) traverses
+ * more nodes per ray (DESIGN.md §5 "Scale and placement"). */
 int gi_scene_create(const gi_scene_desc* desc, gi_scene** out);
 void gi_scene_destroy(gi_scene* scene);
 int gi_scene_get_info(const gi_scene* scene, gi_scene_info* info);

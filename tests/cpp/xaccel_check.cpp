@@ -10,7 +10,7 @@
 //    climb, re-cull against the current best t; k_mode_x walks the same masks without the re-cull)
 //    returns the same closest hit (t, primitive) as a brute-force loop over all primitives, for
 //    closest and any-hit (shadow) queries, on random soups and on the Cornell box.
-//   xaccel_check <n_rays>
+//   xaccel_check <n_rays> [scene.scn]   (the file alone: octree / impsphere / imptriangle lines, rays from its own bounds)
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -22,6 +22,7 @@
 
 #include "gi.h"
 #include "gi_scene.h"
+#include "x_region.h"   // where the rays start and aim: the scene's own bounds
 
 using namespace gi;
 
@@ -270,8 +271,8 @@ static gi_entity_desc tri(double* v) {
     return e;
 }
 
-// optional: a .scn file (impsphere / imptriangle lines only), e.g. the Cornell box
-static bool read_scn(const char* path, std::vector<gi_entity_desc>& ents) {
+// optional: a .scn file (octree / impsphere / imptriangle lines only), e.g. the Cornell box
+static bool read_scn(const char* path, std::vector<gi_entity_desc>& ents, Region& rg) {
     std::ifstream f(path);
     std::string line;
     while (std::getline(f, line)) {
@@ -282,6 +283,8 @@ static bool read_scn(const char* path, std::vector<gi_entity_desc>& ents) {
         double x;
         while (is >> x) v.push_back(x);
         gi_entity_desc e{};
+        if (kw == "octree" && v.size() == 6)
+            for (int k = 0; k < 3; ++k) { rg.oct_lo[k] = v[k]; rg.oct_hi[k] = v[3 + k]; }
         if (kw == "imptriangle") e.kind = GI_IMP_TRIANGLE;
         else if (kw == "impsphere") e.kind = GI_IMP_SPHERE;
         else continue;
@@ -297,7 +300,7 @@ static bool read_scn(const char* path, std::vector<gi_entity_desc>& ents) {
 // |d . n| from 1 down to just above the scene's bound, with the origin's group skipped when the
 // incidence clears the bound: the same closest hit (t, primitive) / the same any-hit answer as brute
 // force.  Below the bound the kernels do not skip; those rays are checked unskipped.  Returns mismatches.
-static long check_plane_skip(const HostScene& hs, int nrays, long& skipped, long& total) {
+static long check_plane_skip(const HostScene& hs, const Region& rg, int nrays, long& skipped, long& total) {
     long bad = 0;
     const int np = (int)hs.xprims.size();
     if (np == 0) return 0;
@@ -305,7 +308,7 @@ static long check_plane_skip(const HostScene& hs, int nrays, long& skipped, long
         const int i = (int)(urand() * np) % np;
         const XPrim& x = hs.xprims[i];
         if (x.kind != 0 || x.pad[0] == 255) continue;
-        const V3 o = (r % 4 == 0) ? v3(-10, 0, 0) : v3(urand() * 12 - 1, urand() * 12 - 6, urand() * 12 - 6);
+        const V3 o = (r % 4 == 0) ? rg.cam : rg.point(urand);
         double a = urand(), b = urand();
         if (a + b > 1) { a = 1 - a; b = 1 - b; }
         const V3 tgt = ld3(x.a) + ld3(x.b) * a + ld3(x.c) * b;
@@ -319,7 +322,7 @@ static long check_plane_skip(const HostScene& hs, int nrays, long& skipped, long
         double tmax = INFINITY;
         const int kind = r % 5;
         if (kind == 0) {   // shadow ray toward a random point
-            const V3 L = v3(urand() * 12 - 1, urand() * 12 - 6, urand() * 12 - 6);
+            const V3 L = rg.point(urand);
             tmax = std::sqrt(sq3(L - P));
             d2 = normalize(L - P);
         } else {           // incidence c: random tangent direction tilted to |d . n| = c, either side
@@ -351,7 +354,11 @@ int main(int argc, char** argv) {
     const int first_scene = argc > 2 ? 4 : 0, last_scene = argc > 2 ? 5 : 4;
     for (int scene = first_scene; scene < last_scene; ++scene) {
         std::vector<gi_entity_desc> ents;
-        if (scene == 4 && !read_scn(argv[2], ents)) return 2;
+        Region rg;
+        if (scene == 4) {
+            if (!read_scn(argv[2], ents, rg)) return 2;
+            rg = region_of(ents, rg);
+        }
         const int ntri = scene == 0 ? 40 : scene == 1 ? 3000 : scene == 2 ? 20000 : scene == 3 ? 300 : 0;
         for (int i = 0; scene == 0 && i < 60; ++i) {   // tilted quads: two triangles in one plane each
             const V3 c = v3(urand() * 10, urand() * 10 - 5, urand() * 10 - 5);
@@ -377,7 +384,7 @@ int main(int argc, char** argv) {
             ents.push_back(e);
         }
         gi_scene_desc sd{};
-        for (int k = 0; k < 3; ++k) { sd.octree_min[k] = -20; sd.octree_max[k] = 20; }
+        for (int k = 0; k < 3; ++k) { sd.octree_min[k] = rg.oct_lo[k]; sd.octree_max[k] = rg.oct_hi[k]; }
         sd.n_entities = (int32_t)ents.size();
         sd.entities = ents.data();
         HostScene hs;
@@ -399,13 +406,13 @@ int main(int argc, char** argv) {
         if (pass == 2) { hs.xwnodes = orig; g_xc = xc.data(); g_xw_base = hs.xwnodes.data(); }
         for (int r = 0; r < nrays; ++r) {
             V3 o, tgt;
-            if (r % 2 == 0) o = v3(-10, 0, 0);
-            else o = v3(urand() * 12 - 1, urand() * 12 - 6, urand() * 12 - 6);
-            tgt = v3(urand() * 12 - 1, urand() * 12 - 6, urand() * 12 - 6);
+            if (r % 2 == 0) o = rg.cam;
+            else o = rg.point(urand);
+            tgt = rg.point(urand);
             if (r % 7 == 0) tgt.y = o.y;   // axis-parallel components
             const V3 d = normalize(tgt - o);
             const bool shadow = (r % 3) == 0;
-            const double tmax = shadow ? 3.0 + 10 * urand() : INFINITY;
+            const double tmax = shadow ? rg.shadow_tmax(urand) : INFINITY;
             double t1, t2;
             const int a = traverse(hs, o, d, shadow, tmax, t1, visits);
             const int b = brute(hs, o, d, shadow, tmax, t2);
@@ -416,11 +423,13 @@ int main(int argc, char** argv) {
         g_xc = nullptr;
         {
             long skipped = 0, tot = 0;
-            const long pb = check_plane_skip(hs, 4 * nrays, skipped, tot);
+            const long pb = check_plane_skip(hs, rg, 4 * nrays, skipped, tot);
             mism += pb;
             std::printf("scene %d plane skip: %ld rays, %ld skipping, bound %.3g + %.3g |cam|, mismatches %ld\n", scene, tot, skipped,
                         hs.x_skip_b, hs.x_skip_a, pb);
         }
+        std::printf("scene %d coordinate reach %.9g: %s the fp32 box tests' limit %.9g\n", scene, x_coord_reach(hs),
+                    x_coord_reach(hs) <= GI_X_COORD_MAX ? "inside" : "BEYOND", GI_X_COORD_MAX);
         std::printf("scene %d: %zu prims, %zu wide nodes, %zu leaf records, depth %d; per ray: %.2f node visits, %.2f prim tests"
                     " (SAH estimate %.2f / %.2f)\n",
                     scene, hs.xprims.size(), hs.xwnodes.size(), hs.xhot.size(), hs.x_max_depth,

@@ -14,7 +14,8 @@
 //  GI_XFLAT_MAX + 1 leaves, tilted coplanar quads, scenes with spheres.  Rays: random, axis-parallel,
 //  and rays leaving computed hit points with the own-plane skip at incidences down to just above the
 //  scene's bound (xaccel_check.cpp check_plane_skip's classes).
-//   xflat_check <n_rays> [cornell.scn]
+//   xflat_check <n_rays> [scene.scn [only]]   (rays of the file's scene from its own bounds, x_region.h;
+//                                              only: the file's scene alone)
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -27,6 +28,7 @@
 
 #include "gi.h"
 #include "gi_scene.h"
+#include "x_region.h"   // where the rays start and aim: the scene's own bounds
 
 using namespace gi;
 
@@ -286,18 +288,18 @@ static bool same(bool shadow, int a, int b, double t1, double t2) {
     return shadow ? ((a >= 0) == (b >= 0)) : (a == b && (t1 == t2 || (std::isinf(t1) && std::isinf(t2))));
 }
 // random and axis-parallel rays
-static long check_rays(const HostScene& hs, int nrays, long& total) {
+static long check_rays(const HostScene& hs, const Region& rg, int nrays, long& total) {
     long bad = 0;
     for (int r = 0; r < nrays; ++r) {
-        V3 o = (r % 2 == 0) ? v3(-10, 0, 0) : v3(urand() * 12 - 1, urand() * 12 - 6, urand() * 12 - 6);
-        V3 tgt = v3(urand() * 12 - 1, urand() * 12 - 6, urand() * 12 - 6);
+        V3 o = (r % 2 == 0) ? rg.cam : rg.point(urand);
+        V3 tgt = rg.point(urand);
         if (r % 7 == 0) tgt.y = o.y;                    // one axis-parallel component
         if (r % 21 == 0) tgt.z = o.z;                   // two
-        if (r % 63 == 0) { o = v3(-10, tgt.y, tgt.z); } // along +x
+        if (r % 63 == 0) { o = rg.cam_yz(tgt); }         // along +x
         if (sq3(tgt - o) == 0.0) continue;
         const V3 d = normalize(tgt - o);
         const bool shadow = (r % 3) == 0;
-        const double tmax = shadow ? 3.0 + 10 * urand() : INFINITY;
+        const double tmax = shadow ? rg.shadow_tmax(urand) : INFINITY;
         double t1, t2;
         const int a = flat_query(hs, o, d, shadow, tmax, t1, 254);
         const int b = brute(hs, o, d, shadow, tmax, t2);
@@ -307,7 +309,7 @@ static long check_rays(const HostScene& hs, int nrays, long& total) {
     return bad;
 }
 // rays leaving computed hit points, the origin's plane group skipped when the incidence clears the bound
-static long check_plane_skip(const HostScene& hs, int nrays, long& skipped, long& total) {
+static long check_plane_skip(const HostScene& hs, const Region& rg, int nrays, long& skipped, long& total) {
     long bad = 0;
     const int np = (int)hs.xprims.size();
     if (np == 0) return 0;
@@ -315,7 +317,7 @@ static long check_plane_skip(const HostScene& hs, int nrays, long& skipped, long
         const int i = (int)(urand() * np) % np;
         const XPrim& x = hs.xprims[i];
         if (x.kind != 0 || x.pad[0] == 255) continue;
-        const V3 o = (r % 4 == 0) ? v3(-10, 0, 0) : v3(urand() * 12 - 1, urand() * 12 - 6, urand() * 12 - 6);
+        const V3 o = (r % 4 == 0) ? rg.cam : rg.point(urand);
         double a = urand(), b = urand();
         if (a + b > 1) { a = 1 - a; b = 1 - b; }
         const V3 tgt = ld3(x.a) + ld3(x.b) * a + ld3(x.c) * b;
@@ -329,7 +331,7 @@ static long check_plane_skip(const HostScene& hs, int nrays, long& skipped, long
         double tmax = INFINITY;
         const int kind = r % 5;
         if (kind == 0) {   // shadow ray toward a random point
-            const V3 L = v3(urand() * 12 - 1, urand() * 12 - 6, urand() * 12 - 6);
+            const V3 L = rg.point(urand);
             tmax = std::sqrt(sq3(L - P));
             d2 = normalize(L - P);
         } else {           // incidence c: random tangent direction tilted to |d . n| = c, either side
@@ -358,9 +360,11 @@ int main(int argc, char** argv) {
     long mism = 0, total = 0;
     // scenes: 0 one leaf, 1 GI_XFLAT_MAX leaves, 2 one more (table only: the scene keeps the tree),
     // 3 tilted coplanar quads, 4 quads and spheres, 5 soup and spheres, 6 the .scn file
-    for (int scene = 0; scene < (argc > 2 ? 7 : 6); ++scene) {
+    const bool only = argc > 3 && std::string(argv[3]) == "only";   // the .scn file alone
+    for (int scene = only ? 6 : 0; scene < (argc > 2 ? 7 : 6); ++scene) {
         std::vector<gi_entity_desc> ents;
         HostScene hs;
+        Region rg;
         if (scene <= 2) {
             if (!soup_with_leaves(scene == 0 ? 1 : GI_XFLAT_MAX + scene - 1, ents, hs)) return 2;
         } else {
@@ -368,6 +372,7 @@ int main(int argc, char** argv) {
             if (scene == 4) { add_quads(ents, 8); for (int i = 0; i < 5; ++i) ents.push_back(sphere()); }
             if (scene == 5) { add_soup(ents, 18, 0.6); for (int i = 0; i < 6; ++i) ents.push_back(sphere()); }
             if (scene == 6 && !read_scn(argv[2], ents)) return 2;
+            if (scene == 6) rg = region_of(ents, rg);
             if (!build(ents, hs)) return 2;
         }
         if (check_table(hs)) return 1;
@@ -380,8 +385,8 @@ int main(int argc, char** argv) {
         if (!hs.x_flat_ok) { std::printf("scene %d: %zu leaves, not eligible\n", scene, leaves); return 1; }
         const long q0 = g_queries, i0 = g_iters, c0 = g_cands;
         long t0 = 0, skipped = 0, tot = 0;
-        const long b1 = check_rays(hs, nrays, t0);
-        const long b2 = check_plane_skip(hs, 4 * nrays, skipped, tot);
+        const long b1 = check_rays(hs, rg, nrays, t0);
+        const long b2 = check_plane_skip(hs, rg, 4 * nrays, skipped, tot);
         mism += b1 + b2;
         total += t0 + tot;
         std::printf("scene %d: %zu prims, %zu leaves; %ld rays + %ld from hit points (%ld skipping, bound %.3g + %.3g |cam|);"

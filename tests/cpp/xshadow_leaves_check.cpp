@@ -16,6 +16,8 @@
 //    1.001 delta from a wall and from two walls at once.  The share of shadow rays that start within 1e-6 of
 //    two planes is printed.
 //   xshadow_leaves_check <rays per light> <cornell.scn> <zoo.scn>
+//   xshadow_leaves_check <rays per light> scenes a.scn ...   (the generic check alone per file, from the file's camera
+//                                                            under the file's light, around the scene's own bounds)
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -310,7 +312,9 @@ static int check_cornell(const SceneFile& sf, HostScene& hs, int nrays, RayStats
 
 // any scene: marked leaves obey the rule; rays from random and camera origins toward random targets and
 // toward points just off the marked planes, lights on either side of them
-static int check_generic(const char* name, HostScene& hs, const double* light, int nrays, RayStats& total) {
+// file_cam: the camera of a .scn file given by itself (`scenes` mode) -- origins, targets and lights are then drawn
+// around the scene's own bounds, not around the world origin, so a scene moved away from it is sampled alike
+static int check_generic(const char* name, HostScene& hs, const double* light, int nrays, RayStats& total, const double* file_cam = nullptr) {
     const int n = (int)hs.xflat.size();
     if (hs.xflat_plane.size() != hs.xflat.size()) { std::printf("%s: xflat_plane has another length\n", name); return 1; }
     const XShadowLeaves sl = shadow_leaves_of(hs);
@@ -325,9 +329,20 @@ static int check_generic(const char* name, HostScene& hs, const double* light, i
         std::printf("%s: %d leaves, not eligible, no marks\n", name, n);
         return 0;
     }
-    const double E = std::max(1.0, hs.x_ext), cam[3] = {-10, 0, 0};
+    const double E = std::max(1.0, hs.x_ext);
+    double cam[3] = {-10, 0, 0}, c[3] = {0, 0, 0}, h[3] = {E, E, E};   // the region: centre and half size
+    if (file_cam) {
+        for (int k = 0; k < 3; ++k) {
+            double lo = INFINITY, hi = -INFINITY;
+            for (const XFlatLeaf& f : hs.xflat) { lo = std::min(lo, (double)f.lo[k]); hi = std::max(hi, (double)f.hi[k]); }
+            cam[k] = file_cam[k];
+            c[k] = 0.5 * (lo + hi);
+            h[k] = 0.5 * (hi - lo);
+        }
+    }
     std::vector<V3> lights = {v3(light[0], light[1], light[2])};
-    for (int i = 0; i < 6; ++i) lights.push_back(v3((2 * urand() - 1) * 1.5 * E, (2 * urand() - 1) * 1.5 * E, (2 * urand() - 1) * 1.5 * E));
+    for (int i = 0; i < 6; ++i)
+        lights.push_back(v3((2 * urand() - 1) * 1.5 * h[0] + c[0], (2 * urand() - 1) * 1.5 * h[1] + c[1], (2 * urand() - 1) * 1.5 * h[2] + c[2]));
     long dead_sum = 0;
     RayStats st;
     for (const V3& L : lights) {
@@ -335,8 +350,9 @@ static int check_generic(const char* name, HostScene& hs, const double* light, i
         const uint32_t live = live_of(hs, Ld, cam);
         dead_sum += n - popc(live);
         for (int r = 0; r < nrays; ++r) {
-            const V3 o = (r % 3 == 0) ? v3(cam[0], cam[1], cam[2]) : v3((2 * urand() - 1) * E, (2 * urand() - 1) * E, (2 * urand() - 1) * E);
-            V3 tgt = v3((2 * urand() - 1) * E, (2 * urand() - 1) * E, (2 * urand() - 1) * E);
+            const V3 o = (r % 3 == 0) ? v3(cam[0], cam[1], cam[2])
+                                      : v3((2 * urand() - 1) * h[0] + c[0], (2 * urand() - 1) * h[1] + c[1], (2 * urand() - 1) * h[2] + c[2]);
+            V3 tgt = v3((2 * urand() - 1) * h[0] + c[0], (2 * urand() - 1) * h[1] + c[1], (2 * urand() - 1) * h[2] + c[2]);
             if (r % 2 == 0 && !hs.xprims.empty()) {   // a point of a primitive, moved by 1e-12 .. 1e-3
                 const XPrim& p = hs.xprims[(size_t)(urand() * hs.xprims.size()) % hs.xprims.size()];
                 double a = urand(), b = urand();
@@ -355,9 +371,19 @@ static int check_generic(const char* name, HostScene& hs, const double* light, i
 }
 
 int main(int argc, char** argv) {
-    if (argc < 4) { std::printf("usage: xshadow_leaves_check <rays per light> <cornell.scn> <zoo.scn>\n"); return 2; }
+    if (argc < 4) { std::printf("usage: xshadow_leaves_check <rays per light> <cornell.scn> <zoo.scn> | <rays per light> scenes a.scn ...\n"); return 2; }
     const int nrays = std::atoi(argv[1]);
     RayStats total;
+    if (std::string(argv[2]) == "scenes") {   // the generic check alone, per file, from the file's camera under the file's light
+        for (int i = 3; i < argc; ++i) {
+            SceneFile sf;
+            HostScene hs;
+            if (!read_scn(argv[i], sf) || !build(sf.ents, hs)) return 2;
+            if (check_generic(argv[i], hs, sf.light, nrays, total, sf.cam)) return 1;
+        }
+        std::printf("rays %ld mismatches %ld\n", total.rays, total.bad);
+        return total.bad == 0 ? 0 : 1;
+    }
     {
         SceneFile sf;
         HostScene hs;

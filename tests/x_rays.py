@@ -29,6 +29,35 @@ LIGHTS = ("scene", "inside", "graze_plane", "behind", "near_1e-7", "far_1e6")
 FAR = {"far_1e3": 1e3, "far_1e6": 1e6}
 
 
+class Frame:
+    """The frame a set's generators work in: the scene's coordinates are x -> s x + off of a base scene's
+    (x_scenes.placed).  Lengths that are absolute in the base frame are multiplied by s, the Cornell
+    blocks' boxes are mapped, and `far` gives the far classes' distances.  The base frame (s = 1, no
+    offset) measures them in extents from the scene's centre, FAR; a placed frame in E = max
+    |coordinate| of the placed scene from the WORLD origin, 32 E and 1e3 E by default -- both beyond
+    the 16 E from which the device tests a ray from a point near the scene (gi_dev.h ray_org32), and
+    near enough for a sphere's quadratic: from 1e6 extents beyond a scene that itself lies 2^20 from
+    the origin a unit sphere's discriminant b^2 - c2 is rounding alone (phantom hits of brute force).
+    `share` gives a hop-1 class that many equal shares of the set instead of one: the placed sets hold
+    1061 rays, a quarter of the base Cornell set, and edge_axis -- whose every ray meets two triangles
+    at one t -- takes two shares there, so that a placed set of the Cornell family still holds at least
+    170 ties."""
+
+    def __init__(self, s=1.0, off=(0.0, 0.0, 0.0), far=None, share=None):
+        self.s, self.off = float(s), np.asarray(off, np.float64)
+        self.placed = far is not None
+        self.far = dict(far) if far is not None else dict(FAR)
+        self.share = dict(share or {})
+
+    def map(self, p):
+        return self.s * np.asarray(p, np.float64) + self.off
+
+
+BASE = Frame()
+PLACED_FAR = {"far_1e3": 32.0, "far_1e6": 1e3}
+PLACED_SHARE = {"edge_axis": 2}
+
+
 def unit(v):
     v = np.asarray(v, np.float64)
     with np.errstate(invalid="ignore", divide="ignore"):
@@ -43,7 +72,7 @@ class Geo:
     primitive of a meshed entity, whose index this module does not derive), the bounds, the pool of
     vertex and bound coordinates per axis, shared edges and boxes to start rays inside."""
 
-    def __init__(self, sc):
+    def __init__(self, sc, frame=BASE):
         tri, known = [], True
         pts = []
         for e in sc.entities:
@@ -88,18 +117,18 @@ class Geo:
                 self.shared_axis.append((a, b, flat[0]))
         name = getattr(sc, "name", "")
         if name.startswith("cornell") or name.startswith("grazing"):   # the Cornell box's two blocks
-            self.boxes = [(np.array([5.0, -3.5, -5.0]), np.array([7.5, -1.0, -2.0])),
-                          (np.array([6.5, 0.5, -5.0]), np.array([9.0, 3.0, 0.5]))]
+            self.boxes = [(frame.map([5.0, -3.5, -5.0]), frame.map([7.5, -1.0, -2.0])),
+                          (frame.map([6.5, 0.5, -5.0]), frame.map([9.0, 3.0, 0.5]))]
         else:   # triangles' own boxes: origins inside leaf boxes
             self.boxes = [(t.min(0), t.max(0)) for t in self.tris[:: max(1, len(self.tris) // 64)]]
 
 
-def hop1(sc, n, seed):
+def hop1(sc, n, seed, frame=BASE):
     """n rays (o, d unit, class index into H1).  Classes a scene cannot have (no triangles, no shared
     edge) give their share to the random classes."""
-    g = Geo(sc)
+    g = Geo(sc, frame)
     rng = np.random.default_rng(seed)
-    per = max(1, n // len(H1))
+    per = max(1, n // (len(H1) + sum(v - 1 for v in frame.share.values())))
     o_all, d_all, c_all = [], [], []
 
     def inside(m):
@@ -162,16 +191,18 @@ def hop1(sc, n, seed):
         # exactly through a point k/32 along a shared edge of two triangles in an axis plane, along that
         # axis from 1, 2 or 4 units off the plane: every operation of the exact tests is exact for
         # vertices with few mantissa bits, so both triangles are hit at one t
+        m = per * frame.share.get("edge_axis", 1)
         ei = rng.integers(0, len(g.shared_axis), m)
         a, b = np.array([g.shared_axis[i][0] for i in ei]), np.array([g.shared_axis[i][1] for i in ei])
         ax = np.array([g.shared_axis[i][2] for i in ei])
         p = a + (rng.integers(1, 32, m) / 32.0)[:, None] * (b - a)
         sgn = np.where(p[np.arange(m), ax] > g.centre[ax], -1.0, 1.0)   # start on the scene's side of the plane
         off = np.zeros((m, 3))
-        off[np.arange(m), ax] = sgn * rng.choice([1.0, 2.0, 4.0], m)
+        off[np.arange(m), ax] = sgn * rng.choice([1.0, 2.0, 4.0], m) * frame.s
         d = np.zeros((m, 3))
         d[np.arange(m), ax] = -sgn
         emit("edge_axis", p + off, d)
+        m = per
     mids = []
     for k in range(3):   # the bounds' 12 edge midpoints
         for u in (g.lo, g.hi):
@@ -190,8 +221,8 @@ def hop1(sc, n, seed):
         emit(name, anywhere(m), unit(d))
     o = outside(m)
     emit("away", o, unit(o - g.centre))
-    for name, f in FAR.items():   # aimed at points of triangles and, every other ray, exactly at a vertex
-        o = g.centre + unit(rng.normal(size=(m, 3))) * (f * g.ext)
+    for name, f in frame.far.items():   # aimed at points of triangles and, every other ray, exactly at a vertex
+        o = (0.0 if frame.placed else g.centre) + unit(rng.normal(size=(m, 3))) * (f * g.ext)
         aim = target(m)
         if have_tri:
             aim[::2] = g.tris.reshape(-1, 3)[rng.integers(0, 3 * len(g.tris), len(aim[::2]))]
@@ -204,11 +235,11 @@ def hop1(sc, n, seed):
     return o[order], d[order], c[order]
 
 
-def complete(sc, o, d, prim1, t1, skip_cos, seed):
+def complete(sc, o, d, prim1, t1, skip_cos, seed, frame=BASE):
     """The records (n, 12) and each ray's H2 and LIGHTS class index (-1: no hop-1 hit, the fields are
     filler).  prim1, t1: the reference's hop-1 answer.  Hits on a primitive without a known triangle
     get random directions and lights that need no normal."""
-    g = Geo(sc)
+    g = Geo(sc, frame)
     rng = np.random.default_rng(seed + 1)
     n = len(o)
     hit = prim1 >= 0
@@ -242,21 +273,22 @@ def complete(sc, o, d, prim1, t1, skip_cos, seed):
     light = np.tile(np.asarray(sc.light, np.float64), (n, 1))
     ins = g.lo + rng.random((n, 3)) * (g.hi - g.lo)
     w = unit(np.cross(nrm, unit(rng.normal(size=(n, 3)))))   # a tangent: the light almost in the hit's plane
-    cand = {"inside": ins, "graze_plane": P + 1.7 * w + 1e-9 * front, "behind": P - 2.0 * front,
-            "near_1e-7": P + 1e-7 * rnd, "far_1e6": P + 1e6 * unit(rng.normal(size=(n, 3)))}
+    s = frame.s   # (the light offsets are lengths of the base frame)
+    cand = {"inside": ins, "graze_plane": P + (1.7 * s) * w + (1e-9 * s) * front, "behind": P - (2.0 * s) * front,
+            "near_1e-7": P + (1e-7 * s) * rnd, "far_1e6": P + (1e6 * s) * unit(rng.normal(size=(n, 3)))}
     for name, v in cand.items():
         sel = lc == LIGHTS.index(name)
         light[sel] = v[sel]
     return np.concatenate([o, d, light, d2], 1), h2, lc
 
 
-def ray_set(sc, n, skip_cos, seed, trace):
+def ray_set(sc, n, skip_cos, seed, trace, frame=BASE):
     """The scene's whole set: dict(recs, h1, h2, light) -- trace(recs) -> dict with prim1 and t1 is the
     reference's query (hop 1 is traced once, with filler lights and directions, to place hop 2)."""
-    o, d, h1 = hop1(sc, n, seed)
+    o, d, h1 = hop1(sc, n, seed, frame)
     filler = np.concatenate([o, d, np.zeros_like(o), np.tile([1.0, 0.0, 0.0], (len(o), 1))], 1)
     r = trace(filler)
-    recs, h2, lc = complete(sc, o, d, r["prim1"], r["t1"], skip_cos, seed)
+    recs, h2, lc = complete(sc, o, d, r["prim1"], r["t1"], skip_cos, seed, frame)
     return dict(recs=recs, h1=h1, h2=h2, light=lc)
 
 
@@ -265,10 +297,10 @@ def near(rs):
     return ~np.isin(rs["h1"], [H1.index(k) for k in FAR])
 
 
-def far_call(rs, name, ext):
+def far_call(rs, name, ext, frame=BASE):
     """(selector, cam_pos) of a far class's call.  The own-plane skip's bound is derived for ray
     origins no farther out than the camera (skip_cos grows with max|cam.pos|, gi_build.cpp
     assign_plane_groups), so the rays that start 1e3 and 1e6 extents out run in calls of their own
     with a camera position of that magnitude; the near rays (rounding of the size of the scene's own
     coordinates, which the bound's 4 E term and its factor of 2000 cover) run with any camera."""
-    return rs["h1"] == H1.index(name), (0.0, -2.0 * FAR[name] * ext, 0.0)
+    return rs["h1"] == H1.index(name), (0.0, -2.0 * frame.far[name] * ext, 0.0)

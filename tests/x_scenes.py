@@ -174,6 +174,115 @@ SHADOW_SCENES = ("cornell", "cornell_mirror", "grazing_floor", "grazing_tilted",
 _sets = {}
 
 
+# ---- scenes at other scales and away from the origin (tests/test_x_placed_host.py, tests/test_gpu_x_placed.py) ----
+# The largest |bound| of a Mode X structure gi_scene_create accepts (gi_scene.h; gi_dev.h inv_dir derives it)
+X_COORD_MAX = float(re.search(r"constexpr double GI_X_COORD_MAX = ([0-9.e+]+);",
+                              open(os.path.join(U.ROOT, "2019global_amd", "csrc", "gi_scene.h")).read()).group(1))
+
+
+def placed(scene, s, off, name=None):
+    """A copy of a scene of ImpTriangles and ImpSpheres under x -> s x + off: every vertex, sphere centre,
+    the camera's position and look-at point, the light and the octree bounds mapped, sphere radii times
+    s, the focal length and the materials as they are.  Other entity kinds are refused."""
+    off = np.asarray(off, np.float64)
+    s = float(s)
+
+    def m(p):
+        return tuple(float(v) for v in s * np.asarray(p, np.float64) + off)
+
+    out = S.Scene(octree_min=m(scene.octree_min), octree_max=m(scene.octree_max), cam_pos=m(scene.cam_pos),
+                  cam_look=m(scene.cam_look), focal=scene.focal, light=m(scene.light), entities=[],
+                  name=name or "%s@%gx+(%g,%g,%g)" % (scene.name, s, *off))
+    for e in scene.entities:
+        if e.kind == S.IMP_TRIANGLE:
+            args = m(e.args[0:3]) + m(e.args[3:6]) + m(e.args[6:9])
+        elif e.kind == S.IMP_SPHERE:
+            args = m(e.args[0:3]) + (e.args[3] * s,) + tuple(e.args[4:])
+        else:
+            raise ValueError("placed(): entity kind %d is neither an ImpTriangle nor an ImpSphere" % e.kind)
+        out.entities.append(S.Entity(e.kind, args, e.material))
+    return out
+
+
+def _limit_scale():
+    """The largest power-of-two scale at which the Cornell box's structure (max |coordinate| 10, padded
+    by 1e-5 of it and rounded outward to fp32) stays within X_COORD_MAX."""
+    k = 0
+    while float(np.nextafter(np.float32(10.0 * (1.0 + 1e-5) * 2.0 ** (k + 1)), np.float32(np.inf))) <= X_COORD_MAX:
+        k += 1
+    return 2.0 ** k
+
+
+# name -> (s, off): power-of-two scales and dyadic offsets, so the Cornell box's coordinates stay exact
+PLACEMENTS = {
+    "x2^-10": (2.0 ** -10, (0.0, 0.0, 0.0)),            # the max(1, ...) floor of the builder's extent
+    "x2^10": (2.0 ** 10, (0.0, 0.0, 0.0)),              # an own-plane skip bound near 0.3
+    "x2^20": (2.0 ** 20, (0.0, 0.0, 0.0)),              # the bound above 1, no dead leaf: no shortcut left
+    "off2^13": (1.0, (8192.0, -4096.0, 2048.0)),
+    "off2^20": (1.0, (2.0 ** 20, 2.0 ** 20, -2.0 ** 20)),   # padding as large as the scene
+    "x2^-10_off2^7": (2.0 ** -10, (128.0, 128.0, -128.0)),  # a small scene 1e4 of its size from the origin
+    "at_limit": (_limit_scale(), (0.0, 0.0, 0.0)),      # just inside the fp32 box tests' limit (2^25)
+    "beyond_limit": (2.0 * _limit_scale(), (0.0, 0.0, 0.0)),   # just outside: gi_scene_create refuses it
+}
+INSIDE = tuple(p for p in PLACEMENTS if p != "beyond_limit")
+PLACED_N = 1024 + 37   # rays per placed set
+# the base scenes placed everywhere, and the one whose build is slow at two placements only
+PLACED_BASES = ("cornell", "cornell_sphere", "grazing_tilted", "corner3_octree", "soup1000")
+PLACED_CASES = [(b, p) for b in PLACED_BASES for p in INSIDE] + [("soup_xcnode", "off2^13"), ("soup_xcnode", "x2^20")]
+# Sets whose farther class (far_1e6, 1e3 E from the world origin by default) starts 32 E out like the
+# nearer one, because at 1e3 E the oracle's BVH and its brute force disagree on the sphere (phantom
+# roots of the quadratic, x_rays.Frame): found by tests/test_x_placed_host.py, which checks every set.
+# At 1e3 E brute force answers the sphere where the BVH does not on 8 of the first set's 66 far_1e6 rays and on 1 of
+# the second's.
+FAR_MOVED_IN = (("cornell_sphere", "off2^20"), ("cornell_sphere", "x2^-10_off2^7"))
+
+
+def placed_scene(base, placement):
+    """(scene, env) of a base query scene at a placement."""
+    sc, env = QUERY_SCENES[base][0]()
+    s, off = PLACEMENTS[placement]
+    return placed(sc, s, off, "%s@%s" % (sc.name, placement)), env
+
+
+def placed_frame(base, placement):
+    import x_rays as R
+    s, off = PLACEMENTS[placement]
+    far = dict(R.PLACED_FAR)
+    if (base, placement) in FAR_MOVED_IN:
+        far["far_1e6"] = far["far_1e3"]
+    return R.Frame(s, off, far, R.PLACED_SHARE)
+
+
+def placed_skip_standin(sc):
+    """Stand-in for the device's skip_cos of a placed scene: every term of the builder's bound but tau
+    grows with E = max |coordinate|, so the base stand-in (E = 10) times E / 10, E floored at 1."""
+    import x_rays as R
+    return STANDIN_SKIP_COS * max(1.0, R.Geo(sc).ext) / 10.0
+
+
+def placed_set(base, placement, skip_cos=None):
+    """(scene, env, ray set, brute-force reference, frame) of a base scene at a placement, as query_set:
+    built once per (scene, placement, skip_cos), read-only afterwards."""
+    import x_rays as R
+    sc, env = placed_scene(base, placement)
+    if skip_cos is None:
+        skip_cos = placed_skip_standin(sc)
+    key = (base, placement, skip_cos)
+    if key not in _sets:
+        frame = placed_frame(base, placement)
+        scn = sc.to_scn()
+        U.oracle_accel(0)
+        try:
+            rs = R.ray_set(sc, PLACED_N, skip_cos, 2019, lambda recs: U.oracle_x_query(scn, recs), frame)
+            ref = U.oracle_x_query(scn, rs["recs"])
+        finally:
+            U.oracle_accel(-1)
+        for a in list(rs.values()) + list(ref.values()):
+            a.setflags(write=False)
+        _sets[key] = (sc, env, rs, ref, frame)
+    return _sets[key]
+
+
 def query_set(name, skip_cos=STANDIN_SKIP_COS):
     """(scene, env, ray set, brute-force reference) of a query scene, built once per (scene, skip_cos)
     and shared by the tests; nothing of it is modified afterwards."""
