@@ -596,6 +596,21 @@ void build_xflat(HostScene& hs) {
     mark_boundary_leaves(hs);
 }
 
+// The table in the device's word order (gi_scene.h XFlatLeafDev): every value as the host record has it.
+std::vector<XFlatLeafDev> xflat_device_table(const HostScene& hs) {
+    std::vector<XFlatLeafDev> t(hs.xflat.size());
+    for (size_t i = 0; i < t.size(); ++i) {
+        const XFlatLeaf& f = hs.xflat[i];
+        XFlatLeafDev& r = t[i];
+        for (int k = 0; k < 3; ++k) { r.lohi[k][0] = f.lo[k]; r.lohi[k][1] = f.hi[k]; }
+        r.off = f.off;
+        r.cnt = f.cnt;
+        r.group = f.group;
+        r.fan = f.fan;
+    }
+    return t;
+}
+
 // Boundary leaves (DESIGN.md §5 "light-dead leaves"): a leaf of the flat table all of whose records are one
 // plane group, with every primitive of the scene on one closed side of the group's plane to within tau, the
 // groups' measured coplanarity.  Primitives are taken by their own geometry -- a triangle's vertices, the

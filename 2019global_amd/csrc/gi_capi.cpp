@@ -504,7 +504,7 @@ int scene_create_on(const gi_scene_desc* desc, int device, gi_scene** out) {
         (e = upload(sp, h.ents, &d.ents)) != hipSuccess || (e = upload(sp, h.tris, &d.tris)) != hipSuccess ||
         (e = upload(sp, h.xwnodes, &d.xwnodes)) != hipSuccess || (e = upload(sp, h.xhot, &d.xhot)) != hipSuccess ||
         (e = upload(sp, h.xbox, &d.xbox)) != hipSuccess ||
-        (e = upload(sp, h.xprims, &d.xprims)) != hipSuccess || (e = upload(sp, h.xflat, &d.xflat)) != hipSuccess ||
+        (e = upload(sp, h.xprims, &d.xprims)) != hipSuccess || (e = upload(sp, xflat_device_table(h), &d.xflat)) != hipSuccess ||
         (e = upload(sp, std::vector<unsigned>(16, 0u), const_cast<const unsigned**>(&d.work))) != hipSuccess ||
         (e = upload(sp, h.app_off, &d.app_off)) != hipSuccess || (e = upload(sp, h.app_rec, &d.app_rec)) != hipSuccess ||
         (e = upload(sp, h.rpath_rec, &d.rpath_rec)) != hipSuccess || (e = upload(sp, h.rc_nodes, &d.rc_nodes)) != hipSuccess ||

@@ -154,6 +154,17 @@ struct XFlatLeaf {         // 32 bytes
     uint8_t fan;           // 1: its two records are a fan pair (gi_fan_pair.h fan_pair_ok); host-side only
 };
 static_assert(sizeof(XFlatLeaf) == 32, "XFlatLeaf layout");
+// The table as the device reads it (DevScene::xflat; xflat_device_table): the same eight words with each
+// axis's two planes side by side, so that a scalar register pair (lo_a, hi_a) is one operand of wf_flat's
+// packed plane distances (DESIGN.md §5 "Two-stage slab distances").  Words 6 and 7 stay where they were.
+struct XFlatLeafDev {      // 32 bytes
+    float lohi[3][2];      // [axis][0: lo, 1: hi]
+    int32_t off;
+    uint16_t cnt;
+    uint8_t group;
+    uint8_t fan;
+};
+static_assert(sizeof(XFlatLeafDev) == 32, "XFlatLeafDev layout");
 // A leaf of the flat table as a boundary of the scene (gi_build.cpp mark_boundary_leaves; DESIGN.md §5
 // "light-dead leaves"): every record of the leaf lies in the plane n . x = c (one plane group), and every
 // primitive of the scene on the closed side(s) named by `sides`.  A shadow ray toward a light that lies on
@@ -276,6 +287,8 @@ inline double x_desc_reach(const gi_scene_desc& desc) {
 }
 // Fills hs.xflat / x_flat_ok from hs.xwnodes (after assign_plane_groups: the group bytes are copied).
 void build_xflat(HostScene& hs);
+// hs.xflat in the device's word order (XFlatLeafDev), record for record: what the scene upload copies.
+std::vector<XFlatLeafDev> xflat_device_table(const HostScene& hs);
 // Fills hs.xflat_plane / x_dead_c from xflat, the plane groups and the primitives (build_xflat calls it).
 void mark_boundary_leaves(HostScene& hs);
 // The launch's copy of them (empty unless the table fits the flat query).
@@ -344,8 +357,9 @@ struct DevScene {
     const int32_t* r_leaf_of_rank;
     int32_t n_r_always;
     float rc_ext;
-    // Mode X flat leaf table (HostScene::xflat), read through the constant cache at wave-uniform addresses
-    const XFlatLeaf* xflat;
+    // Mode X flat leaf table (HostScene::xflat in the device's word order), read through the constant cache at
+    // wave-uniform addresses
+    const XFlatLeafDev* xflat;
     int32_t n_xflat;
     int32_t x_flat;        // 1: the scene is staged in LDS and its table fits (k_seg / k_wf_bounce use wf_flat)
     float x_far_r;         // 16 x max |coordinate| of root_lo / root_hi (inf: no primitive): rays that start

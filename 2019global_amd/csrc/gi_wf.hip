@@ -221,7 +221,7 @@ constexpr size_t kFlatPkBytes = GI_XFLAT_MAX * sizeof(uint32_t);   // the leaves
 typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
 // record k's eight words from the constant address space: a scalar load at a uniform address (a copy
 // of the table staged in LDS and read by broadcast measured 2.5% slower on the Cornell box, round 8)
-__device__ __forceinline__ u32x8 flat_rec_uniform(const XFlatLeaf* tab, int k) {
+__device__ __forceinline__ u32x8 flat_rec_uniform(const XFlatLeafDev* tab, int k) {
     return *(const __attribute__((address_space(4))) u32x8*)(uintptr_t)(tab + k);
 }
 // (offset, index, count) of a candidate in one word: offset < 2^16, count <= 255 (HostScene::x_flat_ok)
@@ -248,12 +248,75 @@ __device__ __forceinline__ float flat_key_floor(int e) { return __int_as_float(e
 // runs on scenes staged in LDS only): an LDS read where a read of the table record in global memory put
 // a cache round trip on every query's path (C3 3.31 -> 3.29 ms, round 8)
 __device__ __forceinline__ uint32_t flat_pk_of(const uint32_t* pkw, int k) { return pkw[k]; }
-// child_hit on a table record read per lane
-__device__ __forceinline__ bool flat_hit(const XFlatLeaf* r, F3 no, F3 ivf, int sm, float tmax, uint32_t& pk, int k) {
+// Phase A's plane distances, two packed fmas per axis (DESIGN.md §5 "Two-stage slab distances").  With ivp the
+// reciprocal where it is positive and +0 otherwise, and ivn the reciprocal where it is negative and +0 otherwise,
+//   near = fma(hi, ivn, fma(lo, ivp, no)),  far = fma(lo, ivn, fma(hi, ivp, no))
+// are child_hit's near / far distances without a select: for a positive reciprocal the inner fma is the plane's
+// distance and the outer adds hi x 0 (or lo x 0) to it; for a negative one the inner fma is 0 + no = no exactly and
+// the outer is child_hit's fma.  The reciprocals are finite and not zero (inv_dir) and the boxes finite, so no
+// 0 x inf arises, and an inner overflow stays the same infinity; only the sign of an exact zero can differ, which
+// no comparison sees.
+//  flat_pk_inner: (fma(lo, ivp, no), fma(hi, ivp, no)) from lh = (lo, hi), iv = (ivp, ivn) and half H of nn.
+//  flat_pk_outer: (near, far) from the same lh with its halves swapped, ivn, and the inner pair.
+// lh is a scalar register pair: two neighbouring words of a record read at a uniform address (XFlatLeafDev).
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+template <int H>
+__device__ __forceinline__ f32x2 flat_pk_inner(f32x2 lh, f32x2 iv, f32x2 nn) {
+    f32x2 r;
+    if constexpr (H == 0) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(r) : "s"(lh), "v"(iv), "v"(nn));
+    else asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,1] op_sel_hi:[1,0,1]" : "=v"(r) : "s"(lh), "v"(iv), "v"(nn));
+    return r;
+}
+__device__ __forceinline__ f32x2 flat_pk_outer(f32x2 lh, f32x2 iv, f32x2 in) {
+    f32x2 r;
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1]" : "=v"(r) : "s"(lh), "v"(iv), "v"(in));
+    return r;
+}
+// The interval of a box from its three (near, far) pairs: tn = max(near x, near y, max(near z, 0)) and
+// tf = min(far x, far y, min(far z, tend)), child_hit's.  As instructions because the compiler does not know that a
+// result of the asm lines above is canonical and would quiet each one before its minimum or maximum (a
+// v_max_f32 x, x per operand); an fma returns no signalling NaN, and tend is canonical where it is made.
+__device__ __forceinline__ float flat_tn(f32x2 px, f32x2 py, f32x2 pz) {
+    float t, r;
+    asm("v_max_f32 %0, 0, %1" : "=v"(t) : "v"(pz.x));
+    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(px.x), "v"(py.x), "v"(t));
+    return r;
+}
+__device__ __forceinline__ float flat_tf(f32x2 px, f32x2 py, f32x2 pz, float tend) {
+    float t, r;
+    asm("v_min_f32 %0, %1, %2" : "=v"(t) : "v"(pz.y), "v"(tend));
+    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(px.y), "v"(py.y), "v"(t));
+    return r;
+}
+// (ivp, ivn) of one reciprocal, by its sign bit as iv_signs takes it
+__device__ __forceinline__ f32x2 flat_iv_pair(float iv) {
+    const bool neg = (int)__float_as_uint(iv) < 0;
+    f32x2 r = {neg ? 0.0f : iv, neg ? iv : 0.0f};
+    return r;
+}
+// the query's operands of the two forms: per axis (ivp, ivn); (no.x, no.y) and (no.z, the interval's end: the
+// pair's other half is not an operand of the fmas, so the bound the far distances are cut at rides in it)
+struct FlatPk {
+    f32x2 ix, iy, iz, nxy, nzt;
+};
+__device__ __forceinline__ FlatPk flat_pk_of_ray(F3 no, F3 ivf, float tend) {
+    FlatPk q;
+    q.ix = flat_iv_pair(ivf.x);
+    q.iy = flat_iv_pair(ivf.y);
+    q.iz = flat_iv_pair(ivf.z);
+    q.nxy = f32x2{no.x, no.y};
+    q.nzt = f32x2{no.z, tend};
+    return q;
+}
+// child_hit on a table record read per lane: the select form, whose distances are Phase A's (above).  The record is
+// the lane's own, so the choice of near and far is made on the planes; the two-stage form here needs the three
+// (ivp, ivn) pairs beside Phase B's fp64 tests and put k_wf_bounce into scratch (DESIGN.md §9 "Round 14").
+__device__ __forceinline__ bool flat_hit(const XFlatLeafDev* r, F3 no, F3 ivf, float tmax, uint32_t& pk, int k) {
     const int4* q = reinterpret_cast<const int4*>(r);
     const int4 a = q[0], b = q[1];
-    const float lx = __int_as_float(a.x), ly = __int_as_float(a.y), lz = __int_as_float(a.z);
-    const float hx = __int_as_float(a.w), hy = __int_as_float(b.x), hz = __int_as_float(b.y);
+    const float lx = __int_as_float(a.x), hx = __int_as_float(a.y), ly = __int_as_float(a.z);
+    const float hy = __int_as_float(a.w), lz = __int_as_float(b.x), hz = __int_as_float(b.y);
+    const int sm = iv_signs(ivf);
     const float nx = (sm & 1) ? hx : lx, fx = (sm & 1) ? lx : hx;
     const float ny = (sm & 2) ? hy : ly, fy = (sm & 2) ? ly : hy;
     const float nz = (sm & 4) ? hz : lz, fz = (sm & 4) ? lz : hz;
@@ -267,19 +330,18 @@ __device__ __forceinline__ bool flat_hit(const XFlatLeaf* r, F3 no, F3 ivf, int 
 // fan (launch-uniform, DevScene::x_fan; the TRI kernels): every leaf is a fan pair, phase B runs one exact test per
 // leaf where the first record's first step decides (gi_fan_pair.h) -- the same (t, primitive) as with both
 template <bool ANY, bool TRI>
-__device__ __forceinline__ int wf_flat(float far_r, const XFlatLeaf* tab, const uint32_t* pkw, int n, const XHot* H, V3 o, V3 d, double tmax, bool act,
+__device__ __forceinline__ int wf_flat(float far_r, const XFlatLeafDev* tab, const uint32_t* pkw, int n, const XHot* H, V3 o, V3 d, double tmax, bool act,
                                        double& t_out, uint32_t& nnode, uint32_t& nprim, uint32_t& nsteps, int skip, bool fan, uint32_t live) {
     const F3 of = ray_org32(o, d, far_r);
     const F3 ivf = inv_dir(d);
     const F3 no = neg_oiv(of, ivf);
-    const int sm = iv_signs(ivf);
-    const bool sx = (sm & 1) != 0, sy = (sm & 2) != 0, sz = (sm & 4) != 0;
     double tb = tmax;
     float tbf = up32(tmax);
     int best = -1;
     // ---- phase A (a lane without a ray: an empty interval, no candidates)
     // (canonical here, once: the minimum it enters would otherwise quiet it again for every leaf)
     const float tfa = __builtin_canonicalizef(act ? tbf : -1.0f);
+    const FlatPk pq = flat_pk_of_ray(no, ivf, tfa);
     // m: the hit bits shifted in, so leaf k ends at bit n - 1 - k.  Closest hit: e1 <= e2, the two
     // smallest candidate keys -- the entry distance's bits (tn >= 0: ordered as integers; -0 sorts first,
     // which is its place) with the low five overwritten by the leaf index, so min / med3 carry the
@@ -288,15 +350,14 @@ __device__ __forceinline__ int wf_flat(float far_r, const XFlatLeaf* tab, const 
     uint32_t m = 0, pk = 0;
     int e1 = kNone, e2 = kNone;
     auto step = [&](const u32x8 w, int k) {
-        const float lx = __uint_as_float(w[0]), ly = __uint_as_float(w[1]), lz = __uint_as_float(w[2]);
-        const float hx = __uint_as_float(w[3]), hy = __uint_as_float(w[4]), hz = __uint_as_float(w[5]);
-        // both planes' distances, then near / far by the reciprocal's sign: child_hit's values (the
-        // planes are scalar operands, so the choice is made on the products)
-        const float ax = __builtin_fmaf(lx, ivf.x, no.x), bx = __builtin_fmaf(hx, ivf.x, no.x);
-        const float ay = __builtin_fmaf(ly, ivf.y, no.y), by = __builtin_fmaf(hy, ivf.y, no.y);
-        const float az = __builtin_fmaf(lz, ivf.z, no.z), bz = __builtin_fmaf(hz, ivf.z, no.z);
-        const float tn = fmaxf(fmaxf(sx ? bx : ax, sy ? by : ay), fmaxf(sz ? bz : az, 0.0f));
-        const float tf = fminf(fminf(sx ? ax : bx, sy ? ay : by), fminf(sz ? az : bz, tfa));
+        // (lo, hi) of each axis: a scalar register pair of the record as loaded
+        const f32x2 lhx = {__uint_as_float(w[0]), __uint_as_float(w[1])}, lhy = {__uint_as_float(w[2]), __uint_as_float(w[3])};
+        const f32x2 lhz = {__uint_as_float(w[4]), __uint_as_float(w[5])};
+        // (near, far) per axis: child_hit's values by two packed fmas, no select (flat_pk_inner)
+        const f32x2 px = flat_pk_outer(lhx, pq.ix, flat_pk_inner<0>(lhx, pq.ix, pq.nxy));
+        const f32x2 py = flat_pk_outer(lhy, pq.iy, flat_pk_inner<1>(lhy, pq.iy, pq.nxy));
+        const f32x2 pz = flat_pk_outer(lhz, pq.iz, flat_pk_inner<0>(lhz, pq.iz, pq.nzt));
+        const float tn = flat_tn(px, py, pz), tf = flat_tf(px, py, pz, pq.nzt.y);
         const bool in = tn <= tf, other = (int)((w[7] >> 16) & 0xFFu) != skip;
         // (the two compares' wave masks, so that their conjunction is the add's carry-in as it stands)
         m = flat_shift_in(m, __builtin_amdgcn_ballot_w64(in) & __builtin_amdgcn_ballot_w64(other));
@@ -352,7 +413,7 @@ __device__ __forceinline__ int wf_flat(float far_r, const XFlatLeaf* tab, const 
     }
 #pragma unroll 1
     for (int k = k0; k < n; ++k) step(flat_rec_uniform(tab, k), k);
-    if (act) nnode += (uint32_t)((n * (int)sizeof(XFlatLeaf) + 255) / 256);
+    if (act) nnode += (uint32_t)((n * (int)sizeof(XFlatLeafDev) + 255) / 256);
     // ---- phase B
     bool go = m != 0;
     if (go) {   // the first candidate: any hit, the lowest bit (the highest leaf, the order of the table's
@@ -436,7 +497,7 @@ __device__ __forceinline__ int wf_flat(float far_r, const XFlatLeaf* tab, const 
                 const int bit = 31 - __builtin_clz(m);   // (the lowest leaf first, as the unshifted mask went)
                 m &= ~(1u << bit);
                 const int k = n - 1 - bit;
-                if (flat_hit(tab + k, no, ivf, sm, tbf, pk, k)) {
+                if (flat_hit(tab + k, no, ivf, tbf, pk, k)) {
                     go = true;
                     break;
                 }
@@ -468,7 +529,7 @@ struct WFView {
     const XHot* LH = nullptr;
     const XPrim* XP = nullptr;
     const REnt* EN = nullptr;
-    const XFlatLeaf* FT = nullptr;   // the flat leaf table phase A reads
+    const XFlatLeafDev* FT = nullptr;   // the flat leaf table phase A reads
     const uint32_t* FP = nullptr;    // FLAT: per leaf its (offset, index, count) word, in LDS (flat_pk_of)
     int* nst = nullptr;
     double* pl = nullptr;   // this lane's L (fields 0-2) and T (3-5), pl[f * 256]
