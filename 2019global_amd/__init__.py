@@ -47,6 +47,8 @@ __all__ = [
     "RayTracer", "DeviceScene", "MODE_R", "MODE_X", "STAT_RAYS", "STAT_NODES", "STAT_PRIMS",
     "STAT_PIXELS", "TILE", "MultiScene", "devices_from_env", "obj_entities", "RAY_DOUBLES",
     "AOV_OUTPUTS", "camera_rays", "camera_rays_device",
+    "PathId", "RadianceParams", "SampleParams", "PATH_ID_DTYPE", "SAMPLE_JITTER",
+    "sample_rays", "sample_rays_device", "resolve_samples", "resolve_samples_device",
     "DenoiseParams", "DENOISE_ALBEDO_STOP", "denoise", "denoise_scratch_bytes", "denoise_device",
     "MOMENTS_OUTPUTS", "DenoiseVarParams", "DENOISE_VAR_OUTPUTS", "DENOISE_VAR_SIGMA_V", "DENOISE_VAR_FLOOR",
     "denoise_var", "denoise_var_scratch_bytes", "denoise_var_device",
@@ -212,6 +214,25 @@ class AdaptiveOut(ctypes.Structure):
                 ("n", ctypes.c_void_p)]
 
 
+SAMPLE_JITTER = 1   # gi.h GI_SAMPLE_JITTER
+# a gi_path_id record as a numpy dtype: the stream (a render's pixel index y w + x) and the sample of a path
+PATH_ID_DTYPE = np.dtype([("stream", "<u8"), ("sample", "<u4"), ("reserved", "<u4")])
+
+
+class PathId(ctypes.Structure):
+    _fields_ = [("stream", ctypes.c_uint64), ("sample", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class RadianceParams(ctypes.Structure):
+    _fields_ = [("depth", ctypes.c_int32), ("flags", ctypes.c_uint32), ("seed", ctypes.c_uint64)]
+
+
+class SampleParams(ctypes.Structure):
+    _fields_ = [("seed", ctypes.c_uint64), ("sample_begin", ctypes.c_int32), ("sample_end", ctypes.c_int32),
+                ("flags", ctypes.c_uint32), ("reserved", ctypes.c_int32), ("aperture", ctypes.c_double),
+                ("focus", ctypes.c_double)]
+
+
 TILE_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint8),
                            ctypes.POINTER(ctypes.c_double))
 
@@ -225,7 +246,9 @@ EXPORTS = ["gi_abi_version", "gi_last_error", "gi_camera_init", "gi_scene_create
            "gi_frame_samples_info", "gi_frame_moments_device", "gi_frame_moments",
            "gi_denoise_var_scratch_bytes", "gi_denoise_var_device", "gi_denoise_var",
            "gi_temporal_device", "gi_temporal",
-           "gi_render_adaptive_device", "gi_render_adaptive", "gi_adaptive_info"]
+           "gi_render_adaptive_device", "gi_render_adaptive", "gi_adaptive_info",
+           "gi_radiance_device", "gi_radiance", "gi_sample_rays_device", "gi_sample_rays",
+           "gi_resolve_samples_device", "gi_resolve_samples"]
 
 _lib = None
 _lock = threading.Lock()
@@ -298,6 +321,13 @@ def lib():
         L.gi_render_adaptive_device.argtypes = ad_args + [vp]
         L.gi_render_adaptive.argtypes = ad_args
         L.gi_adaptive_info.argtypes = [vp, ip, ip, ip, ctypes.POINTER(ctypes.c_int64)]
+        L.gi_radiance_device.argtypes = [vp, i64, vp, vp, dp, ctypes.POINTER(RadianceParams), vp, vp]
+        L.gi_radiance.argtypes = [vp, i64, dp, vp, dp, ctypes.POINTER(RadianceParams), dp]
+        L.gi_sample_rays_device.argtypes = [ctypes.POINTER(CameraDesc), ctypes.POINTER(AovFrame), ctypes.POINTER(SampleParams),
+                                            vp, vp, vp]
+        L.gi_sample_rays.argtypes = [ctypes.POINTER(CameraDesc), ctypes.POINTER(AovFrame), ctypes.POINTER(SampleParams), vp, vp]
+        L.gi_resolve_samples_device.argtypes = [i64, ctypes.c_int32, vp, vp, vp, vp]
+        L.gi_resolve_samples.argtypes = [i64, ctypes.c_int32, dp, vp, vp]
         L.gi_scene_kernel_ms.argtypes =[vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)]
         L.gi_scene_x_form.argtypes = [vp, ctypes.POINTER(Opts), ctypes.POINTER(ctypes.c_int32)]
         L.gi_scene_seg_ring.argtypes = [vp, ctypes.POINTER(Opts), ctypes.POINTER(ctypes.c_int32)]
@@ -343,6 +373,39 @@ def _check_rays(rays) -> int:
             not rays.flags.c_contiguous:
         raise ValueError(f"rays: a C-contiguous float64 array of shape (n, {RAY_DOUBLES}) -- o[3], d[3], tmax, reserved")
     return int(rays.shape[0])
+
+
+def _check_ids(ids, n):
+    """The path ids of a host radiance call: None, or a C-contiguous array of PATH_ID_DTYPE and shape (n,).
+    ValueError otherwise.  Checked before the library is touched."""
+    if ids is None:
+        return None
+    if not isinstance(ids, np.ndarray) or ids.dtype != PATH_ID_DTYPE or ids.shape != (n,) or not ids.flags.c_contiguous:
+        raise ValueError("ids: None or a C-contiguous array of PATH_ID_DTYPE (stream, sample, reserved), one per ray")
+    return ids
+
+
+def _sample_params(seed, samples, jitter, aperture, focus) -> SampleParams:
+    """The gi_sample_params of a call: samples = (begin, end) or a count (0, count).  ValueError for a sample
+    range that is not two integers 0 <= begin <= end, and for an aperture or focus that is not a number."""
+    def whole(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+    if whole(samples):
+        samples = (0, samples)
+    samples = tuple(samples) if isinstance(samples, (tuple, list)) else ()
+    if len(samples) != 2 or not all(whole(v) for v in samples) or not 0 <= samples[0] <= samples[1] < 2 ** 31:
+        raise ValueError("samples: a count, or (begin, end) with 0 <= begin <= end")
+    return SampleParams(int(seed), int(samples[0]), int(samples[1]), SAMPLE_JITTER if jitter else 0, 0, float(aperture),
+                        float(focus))
+
+
+def _check_rows(rows):
+    """(n_pix, ns) of host radiance rows for resolve_samples; ValueError unless rows is a C-contiguous float64
+    array of shape (n_pix, ns, 3) with ns >= 1.  Checked before the library is touched."""
+    if not isinstance(rows, np.ndarray) or rows.dtype != np.float64 or rows.ndim != 3 or rows.shape[2] != 3 or \
+            rows.shape[1] < 1 or not rows.flags.c_contiguous:
+        raise ValueError("rows: a C-contiguous float64 array of shape (n_pix, ns, 3), ns >= 1")
+    return int(rows.shape[0]), int(rows.shape[1])
 
 
 def _aov_frame(w, h, window) -> AovFrame:
@@ -765,6 +828,31 @@ class DeviceScene:
         _check(lib().gi_occluded_device(self._h, int(n), d_rays or None, d_occluded or None, stream or None),
                "gi_occluded_device")
 
+    # ---- radiance along caller-supplied rays (gi.h "radiance") ---------------------------------------
+    def radiance(self, rays: np.ndarray, light, depth: int, ids=None, seed: int = 0, flags: int = 0) -> np.ndarray:
+        """The radiance arriving along host rays (gi_radiance): one Mode X path sample per record of rays
+        ((n, RAY_DOUBLES) float64; d is normalised by the library, tmax is ignored), its random numbers those of
+        ids[i] = (stream, sample) -- a PATH_ID_DTYPE array, None: (i, 0) -- under seed.  Returns (n, 3) float64,
+        unclamped: over sample_rays' records, the rows a render of that frame writes.  flags: FLAG_X_NO_SHADOW
+        only.  ValueError for any other array."""
+        n = _check_rays(rays)
+        ids = _check_ids(ids, n)
+        out = np.empty((max(n, 1), 3), np.float64)
+        p = RadianceParams(int(depth), int(flags), int(seed))
+        dp = ctypes.POINTER(ctypes.c_double)
+        _check(lib().gi_radiance(self._h, n, rays.ctypes.data_as(dp) if n else ctypes.cast(_scratch_ptr(), dp),
+                                 ids.ctypes.data if ids is not None and n else None, _d3(light), ctypes.byref(p),
+                                 out.ctypes.data_as(dp)), "gi_radiance")
+        return out[:n]
+
+    def radiance_device(self, n: int, d_rays: int, d_rgb: int, light, depth: int, d_ids: int = 0, seed: int = 0,
+                        flags: int = 0, stream: int = 0) -> None:
+        """Asynchronous radiance of n device-resident rays into a device buffer of n x 3 float64
+        (gi_radiance_device); pointers are ints, d_ids = 0: stream = i, sample = 0."""
+        p = RadianceParams(int(depth), int(flags), int(seed))
+        _check(lib().gi_radiance_device(self._h, int(n), d_rays or None, d_ids or None, _d3(light), ctypes.byref(p),
+                                        d_rgb or None, stream or None), "gi_radiance_device")
+
     # ---- first-hit feature buffers (gi.h "feature buffers") ------------------------------------------
     def render_aov(self, cam: "Camera", w: int, h: int, window=None, want=AOV_OUTPUTS) -> dict:
         """What each pixel of the window (x0, y0, x1, y1) of a w x h frame shows (gi_render_aov; None: the
@@ -942,6 +1030,54 @@ def camera_rays_device(cam: "Camera", w: int, h: int, d_rays: int, window=None, 
     f = _aov_frame(w, h, window)
     _check(lib().gi_camera_rays_device(ctypes.byref(cam._c), ctypes.byref(f), d_rays or None, stream or None),
            "gi_camera_rays_device")
+
+
+def sample_rays(cam: "Camera", w: int, h: int, samples=1, window=None, seed: int = 0, jitter: bool = True,
+                aperture: float = 0.0, focus: float = 1.0):
+    """The rays a Mode X render traces for the samples (a count, or (begin, end)) of every pixel of the window of a
+    w x h frame, through a thin lens of radius aperture focused at distance focus when aperture > 0
+    (gi_sample_rays): (rays, ids), (rows * cols * ns, RAY_DOUBLES) float64 and (rows * cols * ns,) PATH_ID_DTYPE,
+    laid out [window pixel, row-major][sample] -- DeviceScene.radiance's inputs.  d is not normalised."""
+    f = _aov_frame(w, h, window)
+    p = _sample_params(seed, samples, jitter, aperture, focus)
+    n = (f.y1 - f.y0) * (f.x1 - f.x0) * (p.sample_end - p.sample_begin)
+    rays, ids = np.empty((n, RAY_DOUBLES), np.float64), np.empty(n, PATH_ID_DTYPE)
+    _check(lib().gi_sample_rays(ctypes.byref(cam._c), ctypes.byref(f), ctypes.byref(p),
+                                rays.ctypes.data if n else _scratch_ptr(), ids.ctypes.data if n else _scratch_ptr()),
+           "gi_sample_rays")
+    return rays, ids
+
+
+def sample_rays_device(cam: "Camera", w: int, h: int, d_rays: int, d_ids: int, samples=1, window=None, seed: int = 0,
+                       jitter: bool = True, aperture: float = 0.0, focus: float = 1.0, stream: int = 0) -> None:
+    """Asynchronous sample_rays into device buffers of rows * cols * ns records (rays 16-byte aligned) on the
+    current device (gi_sample_rays_device); pointers are ints, an output of 0 is not written."""
+    f = _aov_frame(w, h, window)
+    p = _sample_params(seed, samples, jitter, aperture, focus)
+    _check(lib().gi_sample_rays_device(ctypes.byref(cam._c), ctypes.byref(f), ctypes.byref(p), d_rays or None,
+                                       d_ids or None, stream or None), "gi_sample_rays_device")
+
+
+def resolve_samples(rows: np.ndarray, want=("rgb", "rgb8")) -> dict:
+    """Per-sample radiance rows (n_pix, ns, 3) to pixels as the renders resolve theirs (gi_resolve_samples): "rgb"
+    (n_pix, 3) float64, the mean of the rows summed in sample order, clamped at 1; "rgb8" (n_pix, 3) uint8."""
+    n_pix, ns = _check_rows(rows)
+    want = tuple(want)
+    if not want or any(k not in ("rgb", "rgb8") for k in want) or len(set(want)) != len(want):
+        raise ValueError('resolve_samples: want is a non-empty selection of ("rgb", "rgb8")')
+    bufs = {"rgb": np.empty((max(n_pix, 1), 3), np.float64), "rgb8": np.empty((max(n_pix, 1), 3), np.uint8)}
+    dp = ctypes.POINTER(ctypes.c_double)
+    _check(lib().gi_resolve_samples(n_pix, ns, rows.ctypes.data_as(dp) if n_pix else ctypes.cast(_scratch_ptr(), dp),
+                                    bufs["rgb"].ctypes.data if "rgb" in want else None,
+                                    bufs["rgb8"].ctypes.data if "rgb8" in want else None), "gi_resolve_samples")
+    return {k: bufs[k][:n_pix] for k in want}
+
+
+def resolve_samples_device(n_pix: int, ns: int, d_rows: int, d_rgb: int = 0, d_rgb8: int = 0, stream: int = 0) -> None:
+    """Asynchronous resolve_samples of device rows [n_pix][ns][3] into device pixels (gi_resolve_samples_device);
+    pointers are ints, an output of 0 is not written."""
+    _check(lib().gi_resolve_samples_device(int(n_pix), int(ns), d_rows or None, d_rgb or None, d_rgb8 or None,
+                                           stream or None), "gi_resolve_samples_device")
 
 
 def _denoise_params(levels, sigma_c, sigma_p, normal_pow_log2, albedo_stop) -> DenoiseParams:

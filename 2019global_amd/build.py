@@ -23,7 +23,7 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 ARCH = "gfx950"
 
 HOST_SRCS = ["gi_build.cpp", "gi_bvh.cpp", "gi_capi.cpp", "gi_multi.cpp", "gi_obj.cpp"]
-DEV_SRCS = ["gi_kernels.hip", "gi_adapt.hip", "gi_mode_r.hip", "gi_wf.hip", "gi_denoise.hip", "gi_temporal.hip"]
+DEV_SRCS = ["gi_kernels.hip", "gi_adapt.hip", "gi_mode_r.hip", "gi_wf.hip", "gi_sample.hip", "gi_denoise.hip", "gi_temporal.hip"]
 HEADERS = ["gi_math.h", "gi_scene.h", "gi_internal.h", "gi_launch.h", "gi_dev.h", "gi_seg_ring.h", "gi_fan_pair.h"]
 
 COMMON = ["-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", f"-I{INCLUDE}", f"-I{CSRC}"]

@@ -1098,6 +1098,170 @@ int gi_camera_rays(const gi_camera* cam, const gi_aov_frame* frame, double* rays
     });
 }
 
+// ---- radiance along caller-supplied rays, sample rays, resolve (gi.h "radiance"; gi_wf.hip k_rad, gi_sample.hip) ----
+// gi_radiance* like the ray queries: the scene's immutable records and launch configuration only, no lock, no
+// ordering against the scene's renders, nothing of the progressive or adaptive frame state is touched.  The
+// other two take no scene.
+namespace {
+// dev: the records are device memory, whose alignment the kernel's loads rely on
+int check_radiance(const gi_scene* s, int64_t n, const double* rays, const gi_path_id* ids, const double* light,
+                   const gi_radiance_params* p, const double* rgb, bool dev) {
+    if (!rays || !light || !p || !rgb) return fail(GI_ERR_ARG, "gi_radiance: null rays, light, params or output");
+    if (n < 0) return fail(GI_ERR_ARG, "negative ray count");
+    if (n >= (int64_t)1 << 32) return fail(GI_ERR_ARG, "gi_radiance: at most 2^32 - 1 records per call");
+    if (p->depth < 1 || p->depth > 0xFFFE) return fail(GI_ERR_ARG, "gi_radiance: 1 <= depth <= 65534");
+    if (p->flags & ~GI_FLAG_X_NO_SHADOW) return fail(GI_ERR_ARG, "gi_radiance: unknown flag (GI_FLAG_X_NO_SHADOW only)");
+    if (dev && (reinterpret_cast<uintptr_t>(rays) & 15)) return fail(GI_ERR_ARG, "device ray records must be 16-byte aligned");
+    if (dev && (reinterpret_cast<uintptr_t>(ids) & 7)) return fail(GI_ERR_ARG, "device path ids must be 8-byte aligned");
+    if (!s) return fail(GI_ERR_ARG, "null scene");   // (last: the other refusals need no scene to be seen)
+    return GI_OK;
+}
+int radiance_device(gi_scene* s, int64_t n, const double* d_rays, const gi_path_id* d_ids, const double* light,
+                    const gi_radiance_params& p, double* d_rgb, hipStream_t stream) {
+    int rc = bind_device(s->device);
+    if (rc) return rc;
+    const RadIO io{d_rays, reinterpret_cast<const uint64_t*>(d_ids), (long long)n, d_rgb, v3(light[0], light[1], light[2]),
+                   p.seed, p.depth, (p.flags & GI_FLAG_X_NO_SHADOW) ? 1 : 0};
+    const hipError_t e = launch_rad(s->dev, x_query_cfg(s->xcfg, 0, WK_RAD), io, stream);
+    return e == hipSuccess ? GI_OK : hip_fail(e, "gi_radiance launch");
+}
+// everything of a gi_sample_rays* call but its outputs; *n: the records (0: nothing to launch)
+int check_sample(const gi_camera* cam, const gi_aov_frame* f, const gi_sample_params* p, int64_t* n) {
+    bool empty = false;
+    const int rc = check_aov_frame(cam, f, &empty);
+    if (rc) return rc;
+    if (!p) return fail(GI_ERR_ARG, "null sample params");
+    if (p->sample_begin < 0 || p->sample_end < p->sample_begin)
+        return fail(GI_ERR_ARG, "gi_sample_rays: 0 <= sample_begin <= sample_end");
+    if (!(p->aperture >= 0.0) || !std::isfinite(p->aperture)) return fail(GI_ERR_ARG, "gi_sample_rays: aperture must be finite and >= 0");
+    if (p->aperture > 0.0 && !(std::isfinite(p->focus) && p->focus > 0.0))
+        return fail(GI_ERR_ARG, "gi_sample_rays: a lens needs a finite focus > 0");
+    if (p->flags & ~GI_SAMPLE_JITTER) return fail(GI_ERR_ARG, "gi_sample_rays: unknown flag");
+    if (p->reserved != 0) return fail(GI_ERR_ARG, "gi_sample_rays: reserved must be 0");
+    const int64_t px = empty ? 0 : (int64_t)(f->x1 - f->x0) * (int64_t)(f->y1 - f->y0), ns = (int64_t)p->sample_end - p->sample_begin;
+    if (px > 0 && ns > 0 && px > (((int64_t)1 << 32) - 1) / ns) return fail(GI_ERR_ARG, "gi_sample_rays: at most 2^32 - 1 records per call");
+    *n = px * ns;
+    return GI_OK;
+}
+SampleIO sample_io(const gi_camera& cam, const gi_aov_frame& f, const gi_sample_params& p, double* rays, gi_path_id* ids) {
+    return SampleIO{f.x0, f.y0, f.x1 - f.x0, f.y1 - f.y0, f.w, p.sample_begin, p.sample_end, (p.flags & GI_SAMPLE_JITTER) ? 1 : 0,
+                    p.seed, p.aperture, p.focus, v3(cam.forward[0], cam.forward[1], cam.forward[2]), rays,
+                    reinterpret_cast<uint64_t*>(ids)};
+}
+int check_resolve(int64_t n_pix, int32_t ns, const double* rows, const double* rgb, const uint8_t* rgb8) {
+    if (n_pix < 0) return fail(GI_ERR_ARG, "negative pixel count");
+    if (ns < 1) return fail(GI_ERR_ARG, "gi_resolve_samples: ns >= 1");
+    if (!rgb && !rgb8) return fail(GI_ERR_ARG, "gi_resolve_samples: every output is null");
+    if (n_pix > 0 && !rows) return fail(GI_ERR_ARG, "null rows");
+    if (rows && rgb == rows) return fail(GI_ERR_ARG, "gi_resolve_samples: rgb must not be the rows' buffer");
+    return GI_OK;
+}
+}  // namespace
+
+int gi_radiance_device(gi_scene* s, int64_t n, const double* d_rays, const gi_path_id* d_ids, const double light[3],
+                       const gi_radiance_params* params, double* d_rgb, void* stream) {
+    return guard([&]() -> int {
+        DeviceRestore keep;   // the caller's current device, restored on return
+        int rc = check_radiance(s, n, d_rays, d_ids, light, params, d_rgb, true);
+        if (rc) return rc;
+        if (n == 0) return GI_OK;
+        return radiance_device(s, n, d_rays, d_ids, light, *params, d_rgb, static_cast<hipStream_t>(stream));
+    });
+}
+
+int gi_radiance(gi_scene* s, int64_t n, const double* rays, const gi_path_id* ids, const double light[3],
+                const gi_radiance_params* params, double* rgb) {
+    return guard([&]() -> int {
+        DeviceRestore keep;   // the caller's current device, restored on return
+        int rc = check_radiance(s, n, rays, ids, light, params, rgb, false);
+        if (rc) return rc;
+        if (n == 0) return GI_OK;
+        if ((rc = bind_device(s->device))) return rc;
+        const size_t m = (size_t)n;
+        DevBuf dr, di, dc;
+        hipError_t e = dr.alloc(m * GI_RAY_DOUBLES * sizeof(double));
+        if (e == hipSuccess && ids) e = di.alloc(m * sizeof(gi_path_id));
+        if (e == hipSuccess) e = dc.alloc(m * 3 * sizeof(double));
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc (radiance staging)");
+        e = hipMemcpy(dr.p, rays, m * GI_RAY_DOUBLES * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess && ids) e = hipMemcpy(di.p, ids, m * sizeof(gi_path_id), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return hip_fail(e, "gi_radiance");
+        rc = radiance_device(s, n, static_cast<const double*>(dr.p), static_cast<const gi_path_id*>(di.p), light, *params,
+                             static_cast<double*>(dc.p), nullptr);
+        if (rc) return rc;
+        e = hipMemcpy(rgb, dc.p, m * 3 * sizeof(double), hipMemcpyDeviceToHost);   // (synchronous copy on the launch's stream)
+        return e == hipSuccess ? GI_OK : hip_fail(e, "gi_radiance");
+    });
+}
+
+int gi_sample_rays_device(const gi_camera* cam, const gi_aov_frame* frame, const gi_sample_params* params, double* d_rays,
+                          gi_path_id* d_ids, void* stream) {
+    return guard([&]() -> int {
+        int64_t n = 0;
+        int rc = check_sample(cam, frame, params, &n);
+        if (rc) return rc;
+        if (!d_rays && !d_ids) return fail(GI_ERR_ARG, "gi_sample_rays: every output is null");
+        if (reinterpret_cast<uintptr_t>(d_rays) & 15) return fail(GI_ERR_ARG, "device ray records must be 16-byte aligned");
+        if (reinterpret_cast<uintptr_t>(d_ids) & 7) return fail(GI_ERR_ARG, "device path ids must be 8-byte aligned");
+        if (n == 0) return GI_OK;
+        const hipError_t e = launch_sample_rays(make_cam(*cam, frame->w), sample_io(*cam, *frame, *params, d_rays, d_ids),
+                                                static_cast<hipStream_t>(stream));
+        return e == hipSuccess ? GI_OK : hip_fail(e, "gi_sample_rays launch");
+    });
+}
+
+int gi_sample_rays(const gi_camera* cam, const gi_aov_frame* frame, const gi_sample_params* params, double* rays,
+                   gi_path_id* ids) {
+    return guard([&]() -> int {
+        int64_t n = 0;
+        int rc = check_sample(cam, frame, params, &n);
+        if (rc) return rc;
+        if (!rays && !ids) return fail(GI_ERR_ARG, "gi_sample_rays: every output is null");
+        if (n == 0) return GI_OK;
+        const size_t m = (size_t)n;
+        DevBuf dr, di;
+        hipError_t e = hipSuccess;
+        if (rays) e = dr.alloc(m * GI_RAY_DOUBLES * sizeof(double));
+        if (e == hipSuccess && ids) e = di.alloc(m * sizeof(gi_path_id));
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc (sample ray staging)");
+        e = launch_sample_rays(make_cam(*cam, frame->w),
+                               sample_io(*cam, *frame, *params, static_cast<double*>(dr.p), static_cast<gi_path_id*>(di.p)), nullptr);
+        if (e == hipSuccess && rays) e = hipMemcpy(rays, dr.p, m * GI_RAY_DOUBLES * sizeof(double), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && ids) e = hipMemcpy(ids, di.p, m * sizeof(gi_path_id), hipMemcpyDeviceToHost);
+        return e == hipSuccess ? GI_OK : hip_fail(e, "gi_sample_rays");
+    });
+}
+
+int gi_resolve_samples_device(int64_t n_pix, int32_t ns, const double* d_rows, double* d_rgb, uint8_t* d_rgb8, void* stream) {
+    return guard([&]() -> int {
+        const int rc = check_resolve(n_pix, ns, d_rows, d_rgb, d_rgb8);
+        if (rc) return rc;
+        if (n_pix == 0) return GI_OK;
+        const hipError_t e = launch_resolve((long long)n_pix, ns, d_rows, d_rgb, d_rgb8, static_cast<hipStream_t>(stream));
+        return e == hipSuccess ? GI_OK : hip_fail(e, "gi_resolve_samples launch");
+    });
+}
+
+int gi_resolve_samples(int64_t n_pix, int32_t ns, const double* rows, double* rgb, uint8_t* rgb8) {
+    return guard([&]() -> int {
+        const int rc = check_resolve(n_pix, ns, rows, rgb, rgb8);
+        if (rc) return rc;
+        if (n_pix == 0) return GI_OK;
+        const size_t m = (size_t)n_pix;
+        DevBuf dr, dc, d8;
+        hipError_t e = dr.alloc(m * (size_t)ns * 3 * sizeof(double));
+        if (e == hipSuccess && rgb) e = dc.alloc(m * 3 * sizeof(double));
+        if (e == hipSuccess && rgb8) e = d8.alloc(m * 3);
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc (resolve staging)");
+        e = hipMemcpy(dr.p, rows, m * (size_t)ns * 3 * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = launch_resolve((long long)n_pix, ns, static_cast<const double*>(dr.p), static_cast<double*>(dc.p),
+                                                static_cast<uint8_t*>(d8.p), nullptr);
+        if (e == hipSuccess && rgb) e = hipMemcpy(rgb, dc.p, m * 3 * sizeof(double), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && rgb8) e = hipMemcpy(rgb8, d8.p, m * 3, hipMemcpyDeviceToHost);
+        return e == hipSuccess ? GI_OK : hip_fail(e, "gi_resolve_samples");
+    });
+}
+
 // ---- sample moments of the retained frame (gi.h "sample moments"; gi_kernels.hip k_x_moments) ----
 // Unlike the queries above these read the scene's Mode X scratch: under the scene's mutex, and ordered on the
 // device with the scene's `last` event in both directions.  Nothing of the progressive-frame state is touched.

@@ -1,4 +1,4 @@
-// gi_launch.h — the host functions that libgi's kernel units (gi_kernels.hip, gi_adapt.hip, gi_mode_r.hip, gi_wf.hip, gi_denoise.hip, gi_temporal.hip)
+// gi_launch.h — the host functions that libgi's kernel units (gi_kernels.hip, gi_adapt.hip, gi_mode_r.hip, gi_wf.hip, gi_sample.hip, gi_denoise.hip, gi_temporal.hip)
 // define for each other and for gi_capi.cpp.  The only place where a cross-unit function is declared: the
 // unit that defines one and the units that call it all include this header.  Host-only, no device code.
 #pragma once
@@ -99,7 +99,7 @@ hipError_t launch_mode_r(const DevScene& sc, const CamDev& cam, V3 light, int w,
 hipError_t launch_trace_ray(const DevScene& sc, V3 o, V3 d, V3 light, int32_t* out_i, double* out_d, hipStream_t stream);
 hipError_t launch_box_kat(int n, const double* recs, int32_t* out, hipStream_t stream);
 
-// ---- gi_wf.hip: k_wf_bounce, k_seg, k_cast, k_aov, k_cam_rays, the query and texel KATs ----
+// ---- gi_wf.hip: k_wf_bounce, k_seg, k_cast, k_aov, k_rad, k_cam_rays, the query and texel KATs ----
 size_t wf_lds_bytes(const DevScene& sc, bool lds, bool flat);   // of k_wf_bounce and its kin, without the ring
 size_t wf_seg_ring_bytes();
 hipError_t wf_occupancy(const DevScene& sc, WfKernel k, const XKernelCfg& c, int* per_cu);
@@ -125,7 +125,28 @@ hipError_t launch_x_texel_kat(const DevScene& sc, XVariant var, int n, int mode,
 hipError_t launch_cast(const DevScene& sc, const XKernelCfg& c, bool any, const CastIO& io, hipStream_t stream);
 hipError_t launch_aov(const DevScene& sc, const XKernelCfg& c, const CamDev& cam, const AovIO& io, hipStream_t stream);
 hipError_t launch_cam_rays(const CamDev& cam, int x0, int y0, int cols, int rows, double* rays, hipStream_t stream);
+// gi_radiance*: k_rad over io's records.  GI_RAD_MAX_GRID (a TEST hook like those of XEnv, but read at every
+// launch): the most workgroups a launch takes.
+hipError_t launch_rad(const DevScene& sc, const XKernelCfg& c, const RadIO& io, hipStream_t stream);
 void wf_variant(const DevScene& sc, const XKernelCfg& c, int32_t out[6]);
+
+// ---- gi_sample.hip: k_sample_rays, k_resolve ----
+// One call of the sample-ray generator (gi_sample_rays*): the window [x0, x0 + cols) x [y0, y0 + rows) of the
+// frame cam was made for, the samples [s0, s1) of every pixel, and the outputs, device pointers laid out
+// [window pixel, row-major][s - s0]; a null output is not written.  fwd: the camera's forward vector (the lens).
+struct SampleIO {
+    int x0, y0, cols, rows, w;
+    int s0, s1;
+    int jitter;
+    uint64_t seed;
+    double aperture, focus;
+    V3 fwd;
+    double* rays;     // GI_RAY_DOUBLES per record, 16-byte aligned
+    uint64_t* ids;    // gi_path_id as two words per record
+};
+hipError_t launch_sample_rays(const CamDev& cam, const SampleIO& io, hipStream_t stream);
+// gi_resolve_samples*: rows [n_pix][ns][3] to the pixels' clamped means and their 8-bit form
+hipError_t launch_resolve(long long n_pix, int ns, const double* rows, double* rgb, uint8_t* rgb8, hipStream_t stream);
 
 // ---- gi_denoise.hip: k_dn_prep, k_dn_level, k_dnv_g, k_dnv_level ----
 // One call of the denoiser (gi_denoise*): the window [x0, x0 + cols) x [y0, y0 + rows) of the frame, its

@@ -471,8 +471,8 @@ enum XForm : int { XFORM_MEGA = 0, XFORM_WF = 1, XFORM_SEG = 2 };
 // (one lane per pixel), the flat phases (k_rf_*), k_mode_r_batch for the whole frame.
 enum RKernel : int { RK_PIXEL = 0, RK_FLAT = 1, RK_BATCH = 2 };
 // gi_wf.hip's kernels whose occupancy is queried per scene (wf_occupancy): k_wf_bounce, k_seg, k_seg with
-// its per-wave ring, k_cast closest hit and any hit, k_aov.
-enum WfKernel { WK_BOUNCE, WK_SEG, WK_SEG_RING, WK_CAST, WK_OCCL, WK_AOV, WK_COUNT };
+// its per-wave ring, k_cast closest hit and any hit, k_aov, k_rad.
+enum WfKernel { WK_BOUNCE, WK_SEG, WK_SEG_RING, WK_CAST, WK_OCCL, WK_AOV, WK_RAD, WK_COUNT };
 
 // Mode X launch configuration, computed once per scene when it is created (gi_capi.cpp, on the
 // scene's device): kernel variant, dynamic LDS bytes and the resident persistent grids.
@@ -497,6 +497,18 @@ struct CastIO {
     int32_t* ent;
     double* nrm;
     int32_t* occl;        // any hit: 1 / 0
+};
+
+// One call of the radiance query (gi_radiance*; gi_wf.hip k_rad): device pointers.
+struct RadIO {
+    const double* rays;     // n records of 8 doubles (o[3], d[3], tmax, reserved), 16-byte aligned
+    const uint64_t* ids;    // n gi_path_id records as two words each (stream; sample | reserved << 32), or null
+    long long n;            // < 2^32 (the path slot's record index, gi_capi.cpp)
+    double* rgb;            // n x 3: the paths' radiance
+    V3 light;
+    uint64_t seed;
+    int depth;
+    int no_shadow;          // GI_FLAG_X_NO_SHADOW
 };
 
 // One call of the feature buffers (gi_render_aov*; gi_wf.hip k_aov): the window [x0, x0 + cols) x

@@ -1280,6 +1280,118 @@ __global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_
     }
 }
 
+// The radiance query (gi_radiance*; DESIGN.md §5 "Radiance query"): what radiance arrives along n
+// caller-supplied rays.  Every record is one path sample: x_segment from its first ray on, in the variant a
+// k_seg launch on the scene runs and with the scene staged as k_seg stages it, so a record that restates a
+// render's jittered primary ray (gi_sample_rays*) gets that render's per-sample row bit for bit.  The path
+// state sits where k_seg keeps it: L and T in the lane's slot fields 0-5, the RNG key in field 6, the record
+// index and the sample in field 7 (idx | smp << 32, idx < 2^32: gi_capi.cpp), the own-plane skip and the bounce
+// index in the plane register.
+// Schedule: a persistent grid that refills without a device counter.  Wave w of the launch's W waves owns the
+// runs w, w + W, ... of kRadRun records.  Each loop iteration is k_seg's direct path minus its atomic: lanes
+// without a path take the next records of the wave's current run by their rank among such lanes (up to
+// GI_SEG_BURST rounds: records that resolve at once leave their lanes free), then every live lane runs one
+// segment, and a lane whose path ended stores L at its record index.  cur, cur_end and next are wave-uniform,
+// and so is every branch of the loop; it ends when the wave has neither a live lane nor a record left.  The
+// call reads the scene's immutable records and its own arguments only, as k_cast.
+// What k_seg decides once per launch from its camera is decided per path here, origins being the caller's:
+//  far_r: the scene's x_far_r always, ray_org32 chooses per lane (k_cast's rule and reasons); bounce rays start
+//    inside the scene and take the near branch, shadow rays pass INFINITY inside x_segment.
+//  the root pretest: wf_primary_misses from the record's o and unnormalised d; a miss stores exact +0.
+//  skip_cos: x_skip_cos of the record's own o.  assign_plane_groups (gi_build.cpp) uses the camera only as the
+//    bound |o| on the origin of the ray whose hit point P the next ray leaves: P's rounding is ~u (|o| + |P| +
+//    ...), and every later origin is a hit point, within the scene's extent E that x_skip_b covers.  The
+//    record's max |o| is that bound for the path's first hit and is kept, larger than needed, for its later ones.
+//  shadow_live: all ones (x_shadow_live returns the full mask where the host cannot bound the origins).
+// Malformed records (a non-finite component of o or d, a zero d) are screened as k_cast screens them: no path,
+// (0, 0, 0) stored, no NaN reaches a comparison that other lanes' control flow shares.
+// Resources (hipcc -S, gfx950): DESIGN.md §9 "Radiance query".
+#ifndef GI_RAD_RUN
+#define GI_RAD_RUN 64   // records per run of k_rad's static schedule
+#endif
+constexpr long long kRadRun = GI_RAD_RUN;
+template <bool LDS, bool W4, bool SH, bool TRI, bool CN, bool FLAT>
+__global__ __launch_bounds__(256, (LDS && W4) ? GI_WF_MIN_WAVES_LDS : GI_WF_MIN_WAVES) void k_rad(DevScene sc, RadIO io) {
+    extern __shared__ int4 lds_dyn[];
+    const WFView v = wf_stage<LDS, FLAT>(sc, lds_dyn);
+    const bool no_shadow = io.no_shadow != 0;
+    const long long hop = kRadRun * (long long)gridDim.x * (long long)(blockDim.x >> 6);
+    // the wave's runs: records [cur, cur_end) of the current one, the next one begins at `next` (uniform)
+    long long next = kRadRun * ((long long)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)));
+    long long cur = 0, cur_end = 0;
+    bool live = false;   // this lane carries a path
+    V3 o = v3(0, 0, 0), d = v3(1, 0, 0), L = v3(0, 0, 0), T = v3(1, 1, 1);
+    int splane = 254;        // the own-plane skip of the lane's next ray | bounce << kSegPlaneBits, as k_seg's
+    double skip_cos = 2.0;   // the path's bound on |d . n| (above)
+    uint32_t nnode = 0, nprim = 0, nrays = 0;
+    WFSegStats ws;
+    for (;;) {
+        // ---- lanes without a path take records
+        for (int burst = 0; burst < GI_SEG_BURST; ++burst) {
+            const unsigned long long m_need = __ballot(!live);
+            if (m_need == 0) break;
+            if (cur == cur_end) {   // the run is used up: the wave's next one
+                if (next >= io.n) break;
+                cur = next;
+                cur_end = min(io.n, next + kRadRun);
+                next += hop;
+            }
+            const unsigned rank = seg_rank(m_need);
+            const unsigned avail = (unsigned)(cur_end - cur), n_need = (unsigned)__popcll(m_need);
+            const long long i = cur + (long long)rank;
+            const bool take = !live && rank < avail;
+            cur += (long long)min(n_need, avail);
+            if (take) {   // i < cur_end <= n; the 64-byte record in three 16-byte loads (tmax, reserved: not read)
+                const double2* q = reinterpret_cast<const double2*>(io.rays) + 4 * i;
+                const double2 q0 = q[0], q1 = q[1], q2 = q[2];
+                const V3 ro = v3(q0.x, q0.y, q1.x), rd = v3(q1.y, q2.x, q2.y);
+                const bool fin = __builtin_isfinite(ro.x) & __builtin_isfinite(ro.y) & __builtin_isfinite(ro.z) &
+                                 __builtin_isfinite(rd.x) & __builtin_isfinite(rd.y) & __builtin_isfinite(rd.z);
+                const bool nz = (rd.x != 0.0) | (rd.y != 0.0) | (rd.z != 0.0);
+                CamDev at{};   // (wf_primary_misses reads the position only)
+                at.pos = ro;
+                if (fin && nz && !wf_primary_misses(sc, at, rd)) {
+                    uint64_t stream = (uint64_t)i, smp = 0;
+                    if (io.ids) {
+                        stream = io.ids[2 * i];
+                        smp = io.ids[2 * i + 1] & 0xFFFFFFFFull;
+                    }
+                    live = true;
+                    o = ro;
+                    d = normalize(rd);
+                    splane = 254;
+                    skip_cos = x_skip_cos(sc, ro);
+                    v.pl[0] = 0.0; v.pl[256] = 0.0; v.pl[512] = 0.0;
+                    v.pl[768] = 1.0; v.pl[1024] = 1.0; v.pl[1280] = 1.0;
+                    slot_put_u64(v.pl, 6, mx_key(io.seed, stream));
+                    slot_put_u64(v.pl, 7, (uint64_t)(uint32_t)i | (smp << 32));
+                } else {
+                    double* r = io.rgb + 3 * i;
+                    r[0] = 0.0; r[1] = 0.0; r[2] = 0.0;
+                }
+            }
+        }
+        if (__ballot(live) == 0) {
+            if (cur == cur_end && next >= io.n) break;
+            continue;
+        }
+        // ---- one segment of every live path
+        const bool cont = x_segment<false, LDS, SH, TRI, CN, FLAT>(
+            sc, v, io.light, io.depth, no_shadow, live,
+            [&] { return PathId{slot_get_u64(v.pl, 6), (unsigned)(slot_get_u64(v.pl, 7) >> 32), splane >> kSegPlaneBits}; },
+            o, d, L, T, nnode, nprim, nrays, ws, skip_cos, &splane, sc.x_far_r, ~0u);
+        if (live) {
+            if (cont) {
+                splane += 1 << kSegPlaneBits;   // the next bounce
+            } else {
+                double* r = io.rgb + 3 * (long long)(uint32_t)slot_get_u64(v.pl, 7);
+                r[0] = L.x; r[1] = L.y; r[2] = L.z;
+                live = false;
+            }
+        }
+    }
+}
+
 // Lane-to-pixel mapping of the feature-buffer kernels: batch b (64 lanes) of a cols x rows window takes
 // the 64 consecutive window pixels 64 b .. 64 b + 63 in row order, so every plane store of a wave is one
 // contiguous run (512 B of t, 1536 B of normals, ...).  The alternative, 8 x 8 tiles as the renders map
@@ -1435,6 +1547,9 @@ constexpr auto cast_kernel(V) { return &k_cast<ANY, V::lds, V::w4, V::sh, V::tri
 
 template <typename V>
 constexpr auto aov_kernel(V) { return &k_aov<V::lds, V::w4, V::sh, V::tri, V::cn, V::flat>; }
+
+template <typename V>
+constexpr auto rad_kernel(V) { return &k_rad<V::lds, V::w4, V::sh, V::tri, V::cn, V::flat>; }
 }  // namespace
 
 XKernelCfg x_query_cfg(const XLaunchCfg& xc, int flags, WfKernel k) {
@@ -1456,6 +1571,7 @@ hipError_t wf_occupancy(const DevScene& sc, WfKernel k, const XKernelCfg& c, int
             case WK_CAST: f = reinterpret_cast<const void*>(cast_kernel<false>(V)); break;
             case WK_OCCL: f = reinterpret_cast<const void*>(cast_kernel<true>(V)); break;
             case WK_AOV: f = reinterpret_cast<const void*>(aov_kernel(V)); break;
+            case WK_RAD: f = reinterpret_cast<const void*>(rad_kernel(V)); break;
             case WK_COUNT: break;
         }
         e = f ? hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, f, 256, c.lds_bytes) : hipErrorInvalidValue;
@@ -1572,6 +1688,24 @@ hipError_t launch_aov(const DevScene& sc, const XKernelCfg& c, const CamDev& cam
     const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>(want, c.resident))), block(256);
     wf_dispatch(sc, c, false, [&](auto V) {
         hipLaunchKernelGGL(aov_kernel(V), grid, block, c.lds_bytes, stream, sc, cam, io);
+    });
+    return hipGetLastError();
+}
+
+// The radiance query's launch: k_rad in k_seg's variant for the scene (wf_dispatch) over a persistent grid of at
+// most c.resident workgroups (wf_occupancy WK_RAD), fewer when the records need fewer: a wave per run.
+// GI_RAD_MAX_GRID (a TEST hook, read at every launch so that one process can set and clear it): at most that
+// many workgroups, so that a small batch gives every wave several runs.  Asynchronous on `stream`; no
+// allocation, no copy, no synchronisation.
+hipError_t launch_rad(const DevScene& sc, const XKernelCfg& c, const RadIO& io, hipStream_t stream) {
+    if (io.n <= 0) return hipSuccess;
+    long long want = std::min<long long>((io.n + 4 * kRadRun - 1) / (4 * kRadRun), c.resident);
+    if (const char* e = std::getenv("GI_RAD_MAX_GRID")) {
+        if (std::atoi(e) > 0) want = std::min<long long>(want, std::atoi(e));
+    }
+    const dim3 grid((unsigned)std::max<long long>(1, want)), block(256);
+    wf_dispatch(sc, c, false, [&](auto V) {
+        hipLaunchKernelGGL(rad_kernel(V), grid, block, c.lds_bytes, stream, sc, io);
     });
     return hipGetLastError();
 }

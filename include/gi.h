@@ -28,6 +28,11 @@
  *                        hits and blends them with it: samples kept while the camera moves (no reference counterpart)
  *   gi_render_adaptive*  a Mode X frame in sample passes that stop tracing the pixels whose error estimate has
  *                        fallen below a tolerance (no reference counterpart)
+ *   gi_radiance*         Mode X's path tracer on caller-supplied rays: one path sample per ray record, its
+ *                        radiance out (no reference counterpart)
+ *   gi_sample_rays*      the rays a Mode X render traces for a frame's pixel samples, optionally through a thin
+ *                        lens, as records for gi_radiance*
+ *   gi_resolve_samples*  per-sample radiance rows to pixels, as the renders resolve theirs
  *   gi_unshard_device    reassembles a frame from per-rank packed tiles after the RCCL gather
  *   gi_scene_kernel_ms   HIP-event duration of the last timed render's dominant kernel (bench)
  *   gi_scene_x_form      which Mode X form (persistent kernel / wavefront) a render would run
@@ -692,6 +697,97 @@ int gi_render_adaptive_device(gi_scene* scene, const gi_camera* cam, const doubl
 int gi_render_adaptive(gi_scene* scene, const gi_camera* cam, const double light[3], int w, int h, const gi_opts* opts,
                        const gi_adaptive_params* params, const gi_adaptive_out* out);
 int gi_adaptive_info(gi_scene* scene, int32_t* w, int32_t* h, int32_t* samples_done, int64_t* active);
+
+/* ---- radiance along caller-supplied rays, sample rays, resolve (ABI 21: added functions only) ---------
+ * What radiance arrives along this ray?  gi_radiance* runs Mode X's path tracer on n rays of the caller's:
+ * every record is one path sample and yields one radiance row.  gi_sample_rays* writes the rays a render
+ * traces for a frame's pixel samples (optionally through a thin lens) and gi_resolve_samples* turns rows into
+ * pixels, so the three calls together are a renderer whose camera and sampling pattern the caller may replace.
+ *
+ * gi_radiance*.  rays: n records of GI_RAY_DOUBLES doubles as gi_intersect takes them (o[3], d[3], tmax,
+ * reserved); tmax and reserved are ignored (a path's first ray has no far end).  ids: n gi_path_id records, or
+ * NULL for stream = i, sample = 0.  rgb: n*3 fp64, the path's radiance L, unclamped.
+ *   The path   the oracle's sample_mode_x from its first ray on: o as given and d = normalize(d) -- d IS
+ *              normalised here, as the renders and gi_trace_ray do and unlike gi_intersect.  A caller who
+ *              wants a render's bits passes the unnormalised pixel direction, as gi_sample_rays* writes it;
+ *              gi_camera_rays' unit d is normalised a second time and may differ in the last place.
+ *              Then the render's segment per bounce b = 0 .. depth-1: the closest hit over t > 1e-7, the
+ *              shadow ray to `light`, the texel, Blinn-Phong, L += T * min(local, 1), the mirror choice on
+ *              dim 4, else T *= texel / 2 (the path ends where T == 0) and the cosine-weighted direction on
+ *              dims 2 and 3.  It is answered by the kernel variant a Mode X render of the scene runs.
+ *   Random numbers  key = mx_key(seed, stream) and every draw is mx_u01k(key, sample, b, dim): stream takes the
+ *              place of a render's pixel index y*w + x and sample that of its sample index.  The row of
+ *              (stream, sample) over a render's own jittered primary ray is therefore the row that render
+ *              writes for the sample (gi_frame_moments' samples plane), bit for bit, and with one sample per
+ *              pixel min(row, 1) is the render's pixel.
+ *   params     depth in [1, 65534] (bounce indices 0xFFFF and 0xFFFE belong to the jitter and the lens below);
+ *              flags: GI_FLAG_X_NO_SHADOW only, as in a render; any other bit is GI_ERR_ARG.
+ *   Malformed  a record with a non-finite component of o or d or a zero d is screened before any traversal
+ *              and yields (0, 0, 0); the other records of the call are not affected.
+ *   Arguments  GI_ERR_ARG for n < 0 or n >= 2^32 and for a NULL scene, rays, light, params or rgb (ids may be
+ *              NULL); otherwise n == 0 launches nothing and returns GI_OK.  Device ray records are 16-byte
+ *              aligned and device ids 8-byte aligned (GI_ERR_ARG otherwise).
+ *   Scene state  as the ray queries: only the scene's immutable records are read, none of its Mode X scratch is
+ *              touched, no device counter is used, the call is not ordered against the scene's renders, and a
+ *              call between two progressive or adaptive passes ends neither frame.
+ *
+ * gi_sample_rays*.  For the window [x0, x1) x [y0, y1) of a w x h frame and the samples [sample_begin,
+ * sample_end) of each of its pixels: one ray record and one gi_path_id per (pixel, sample), laid out
+ * [window pixel, row-major][s - sample_begin]; either output may be NULL (both: GI_ERR_ARG).  No scene: it runs
+ * on the current HIP device, like gi_camera_rays.  Everything is fp64, no operation is contracted, dots are
+ * (x x' + y y') + z z'.  With left, up, top_left and res the renders' frame vectors (gi_render_aov above), per
+ * pixel (x, y) and sample s:
+ *   stream = y w + x;  key = mx_key(seed, stream);  id = (stream, s, 0)
+ *   GI_SAMPLE_JITTER: jx = mx_u01k(key, s, 0xFFFF, 0), jy = mx_u01k(key, s, 0xFFFF, 1) -- what a render with
+ *              spp > 1 draws; without the flag jx = jy = 0, a 1-spp render's ray
+ *   d0 = (top_left - (left (x + jx)) res) - (up (y + jy)) res, NOT normalised
+ *   aperture == 0:  o = pos, d = d0.  gi_radiance over these records is the render's rows bit for bit.
+ *   aperture > 0:   (lx, ly) = mx_disk(mx_u01k(key, s, 0xFFFE, 0), mx_u01k(key, s, 0xFFFE, 1)), the concentric
+ *              map of the unit square onto the unit disk that the cosine sampling uses;
+ *              q = focus / ((d0.x f.x + d0.y f.y) + d0.z f.z) with f the camera's forward;
+ *              F = pos + d0 q  (the point of the pinhole ray at distance `focus` along forward);
+ *              o = (pos + left (aperture lx)) + up (aperture ly);   d = F - o.
+ *   tmax = +inf, reserved = 0.
+ *   Arguments  GI_ERR_ARG for a bad frame, window or camera as gi_render_aov judges them; a NULL params;
+ *              sample_begin < 0 or sample_end < sample_begin; an aperture that is negative or not finite;
+ *              aperture > 0 with a focus that is not finite and > 0; an unknown flag; reserved != 0; both outputs
+ *              NULL; more than 2^32 - 1 records; device ray records that are not 16-byte aligned (ids: 8-byte).
+ *              An empty window or an empty sample range launches nothing and returns GI_OK.
+ *
+ * gi_resolve_samples*.  rows: [n_pix][ns][3] fp64.  Per pixel and channel sum = +0, sum = sum + x_s in sample
+ * order, mean = sum / (double)ns, rgb = mean < 1 ? mean : 1 and rgb8 = the renders' 8-bit quantisation of rgb:
+ * the operations a render resolves its rows with.  Either output may be NULL (both: GI_ERR_ARG).  GI_ERR_ARG
+ * for ns < 1, n_pix < 0, NULL rows with n_pix > 0, or an rgb that is the rows' own buffer; n_pix == 0 launches
+ * nothing.  No scene.
+ *
+ * The _device variants take device pointers and are asynchronous on `stream` (hipStream_t; NULL = default
+ * stream): they make no allocation, no host synchronisation and no copy.  The others do the same from / into
+ * host buffers (stage, launch, copy back) and are synchronous.
+ * Not provided: Mode R; shards and gi_multi; the C++ drop-in headers; GI_FLAG_STATS / GI_FLAG_TIME; a tmax on
+ * the first ray; adaptive stopping; a retained frame (gi_frame_moments does not see these rows: the caller
+ * has them). */
+#define GI_SAMPLE_JITTER 1u   /* gi_sample_params.flags: jitter each sample inside its pixel, as a render with spp > 1 */
+typedef struct gi_path_id { uint64_t stream; uint32_t sample; uint32_t reserved; } gi_path_id;
+typedef struct gi_radiance_params { int32_t depth; uint32_t flags; uint64_t seed; } gi_radiance_params;
+typedef struct gi_sample_params {
+    uint64_t seed;
+    int32_t sample_begin, sample_end;   /* the samples [sample_begin, sample_end) of every pixel */
+    uint32_t flags;                     /* GI_SAMPLE_* */
+    int32_t reserved;                   /* 0 */
+    double aperture;                    /* lens radius, 0 = pinhole */
+    double focus;                       /* aperture > 0: distance along forward of the plane in focus */
+} gi_sample_params;
+int gi_radiance_device(gi_scene* scene, int64_t n, const double* d_rays, const gi_path_id* d_ids, const double light[3],
+                       const gi_radiance_params* params, double* d_rgb, void* stream);
+int gi_radiance(gi_scene* scene, int64_t n, const double* rays, const gi_path_id* ids, const double light[3],
+                const gi_radiance_params* params, double* rgb);
+int gi_sample_rays_device(const gi_camera* cam, const gi_aov_frame* frame, const gi_sample_params* params,
+                          double* d_rays, gi_path_id* d_ids, void* stream);
+int gi_sample_rays(const gi_camera* cam, const gi_aov_frame* frame, const gi_sample_params* params, double* rays,
+                   gi_path_id* ids);
+int gi_resolve_samples_device(int64_t n_pix, int32_t ns, const double* d_rows, double* d_rgb, uint8_t* d_rgb8,
+                              void* stream);
+int gi_resolve_samples(int64_t n_pix, int32_t ns, const double* rows, double* rgb, uint8_t* rgb8);
 
 /* Average duration in ms of the dominant kernel over the scene's renders issued with GI_FLAG_TIME
  * since the previous call (waits for the last one; *n = how many, may be NULL), then resets.
