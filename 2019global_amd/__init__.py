@@ -238,7 +238,7 @@ TILE_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ct
 
 EXPORTS = ["gi_abi_version", "gi_last_error", "gi_camera_init", "gi_scene_create", "gi_scene_destroy",
            "gi_scene_get_info", "gi_render", "gi_render_device", "gi_shard_tiles", "gi_unshard_device",
-           "gi_trace_ray", "gi_kat_expbox", "gi_kat_x_query", "gi_kat_x_variant", "gi_kat_x_texel", "gi_scene_kernel_ms", "gi_scene_x_form", "gi_scene_seg_ring", "gi_scene_shadow_leaves", "gi_scene_r_kernel", "gi_octree_create", "gi_octree_destroy",
+           "gi_trace_ray", "gi_kat_expbox", "gi_kat_r_prims", "gi_kat_r_entities", "gi_kat_x_query", "gi_kat_x_variant", "gi_kat_x_texel", "gi_scene_kernel_ms", "gi_scene_x_form", "gi_scene_seg_ring", "gi_scene_shadow_leaves", "gi_scene_r_kernel", "gi_octree_create", "gi_octree_destroy",
            "gi_octree_intersect", "gi_multi_create", "gi_multi_destroy", "gi_multi_info", "gi_multi_render", "gi_device_count",
            "gi_device_list", "gi_build_id", "gi_obj_parse", "gi_intersect", "gi_occluded", "gi_intersect_device",
            "gi_occluded_device", "gi_render_aov", "gi_render_aov_device", "gi_camera_rays", "gi_camera_rays_device",
@@ -285,6 +285,8 @@ def lib():
         L.gi_trace_ray.argtypes = [vp, dp, dp, dp, ctypes.POINTER(Hit), dp]
         L.gi_kat_expbox.argtypes = [i32, dp, ctypes.POINTER(ctypes.c_int32)]
         ip = ctypes.POINTER(ctypes.c_int32)
+        L.gi_kat_r_prims.argtypes = [i32, i32, dp, ip, dp]
+        L.gi_kat_r_entities.argtypes = [vp, i32, dp, ip, dp]
         L.gi_kat_x_query.argtypes = [vp, i32, dp, dp, i32, ip, dp, ip, ip, ip, dp, ip, dp]
         L.gi_kat_x_variant.argtypes = [vp, i32, ip]
         L.gi_kat_x_texel.argtypes = [vp, i32, dp, i32, dp, ip]
@@ -957,6 +959,18 @@ class DeviceScene:
         _check(lib().gi_adaptive_info(self._h, *(ctypes.byref(x) for x in v), ctypes.byref(act)), "gi_adaptive_info")
         return {"w": int(v[0].value), "h": int(v[1].value), "samples_done": int(v[2].value), "active": int(act.value)}
 
+    def kat_r_entities(self, rays: np.ndarray) -> dict:
+        """Every ray (o, dir; 6 doubles, dir normalised on the device) against every entity through the
+        Mode R kernels' entity test (gi_kat_r_entities; a test hook): hit (n, E) int32 and pn (n, E, 6)."""
+        rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
+        n, ne = rays.shape[0], self.info()["n_entities"]
+        hit = np.zeros((n, ne), np.int32)
+        pn = np.zeros((n, ne, 6))
+        _check(lib().gi_kat_r_entities(self._h, n, rays.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                       hit.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                       pn.ctypes.data_as(ctypes.POINTER(ctypes.c_double))), "gi_kat_r_entities")
+        return dict(hit=hit, pn=pn)
+
     def kat_x_variant(self, flags: int = 0) -> dict:
         """The kernel variant kat_x_query runs with these flags (flags 0: k_seg's for this scene):
         {"LDS", "W4", "SH", "TRI", "CN", "FLAT"} -> bool (gi_kat_x_variant)."""
@@ -1360,6 +1374,25 @@ def kat_expbox(recs: np.ndarray) -> np.ndarray:
     _check(lib().gi_kat_expbox(recs.shape[0], recs.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
                                out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), "gi_kat_expbox")
     return out
+
+
+KAT_R_TRI, KAT_R_SPHERE, KAT_R_BOX, KAT_R_BOX4 = 0, 1, 2, 3
+_KAT_R_WIDTH = {KAT_R_TRI: 15, KAT_R_SPHERE: 10, KAT_R_BOX: 12, KAT_R_BOX4: 12}
+
+
+def kat_r_prims(kind: int, recs: np.ndarray) -> dict:
+    """Mode R's primitive tests on the device, record by record (gi_kat_r_prims; a test hook): triangles
+    (p1 p2 p3 o dir), spheres (pos radius o dir), boxes (min max o dir) by one lane or by the grouped
+    node test.  hit (n,) int32; pn (n, 6) point and normal for triangles and spheres, None for boxes."""
+    recs = np.ascontiguousarray(recs, np.float64).reshape(-1, _KAT_R_WIDTH[kind])
+    n = recs.shape[0]
+    hit = np.zeros(n, np.int32)
+    pn = np.zeros((n, 6)) if kind in (KAT_R_TRI, KAT_R_SPHERE) else None
+    _check(lib().gi_kat_r_prims(int(kind), n, recs.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                hit.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                pn.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if pn is not None else None),
+           "gi_kat_r_prims")
+    return dict(hit=hit, pn=pn)
 
 
 def shard_tiles(w: int, h: int, shard_count: int) -> int:

@@ -1800,6 +1800,67 @@ int gi_kat_expbox(int n, const double* recs, int32_t* out) {
     });
 }
 
+int gi_kat_r_prims(int kind, int n, const double* recs, int32_t* hit, double* pn) {
+    return guard([&]() -> int {
+        if (kind < GI_KAT_R_TRI || kind > GI_KAT_R_BOX4) return fail(GI_ERR_ARG, "bad kind");
+        const bool with_pn = kind == GI_KAT_R_TRI || kind == GI_KAT_R_SPHERE;
+        if (n < 0 || (n > 0 && (!recs || !hit || (with_pn && !pn)))) return fail(GI_ERR_ARG, "bad arguments");
+        if (n == 0) return GI_OK;
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(GI_ERR_DEVICE, "no HIP device");
+        const size_t width = kind == GI_KAT_R_TRI ? 15 : kind == GI_KAT_R_SPHERE ? 10 : 12;
+        const size_t rb = (size_t)n * width * sizeof(double), hb = (size_t)n * sizeof(int32_t), pb = (size_t)n * 6 * sizeof(double);
+        std::vector<TriRec> tris;
+        if (kind == GI_KAT_R_TRI) {   // the builder's records (gi_build.cpp builds an ImpTriangle's with make_tri too)
+            tris.resize((size_t)n);
+            for (int i = 0; i < n; ++i) {
+                const double* q = recs + 15 * (size_t)i;
+                make_tri(v3(q[0], q[1], q[2]), v3(q[3], q[4], q[5]), v3(q[6], q[7], q[8]), tris[(size_t)i]);
+            }
+        }
+        DevBuf d_r, d_t, d_h, d_p;
+        hipError_t e = d_r.alloc(rb);
+        if (e == hipSuccess) e = d_h.alloc(hb);
+        if (e == hipSuccess && with_pn) e = d_p.alloc(pb);
+        if (e == hipSuccess && !tris.empty()) e = d_t.alloc(tris.size() * sizeof(TriRec));
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc (gi_kat_r_prims)");
+        e = hipMemcpy(d_r.p, recs, rb, hipMemcpyHostToDevice);
+        if (e == hipSuccess && !tris.empty()) e = hipMemcpy(d_t.p, tris.data(), tris.size() * sizeof(TriRec), hipMemcpyHostToDevice);
+        if (e == hipSuccess)
+            e = launch_r_prims_kat(kind, n, static_cast<const double*>(d_r.p), static_cast<const TriRec*>(d_t.p),
+                                   static_cast<int32_t*>(d_h.p), static_cast<double*>(d_p.p), nullptr);
+        if (e == hipSuccess) e = hipMemcpy(hit, d_h.p, hb, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && with_pn) e = hipMemcpy(pn, d_p.p, pb, hipMemcpyDeviceToHost);
+        return e == hipSuccess ? GI_OK : hip_fail(e, "gi_kat_r_prims");
+    });
+}
+
+int gi_kat_r_entities(gi_scene* s, int n, const double* rays, int32_t* hit, double* pn) {
+    return guard([&]() -> int {
+        DeviceRestore keep;   // the caller's current device, restored on return
+        if (!s || n < 0 || (n > 0 && (!rays || !hit || !pn))) return fail(GI_ERR_ARG, "bad arguments");
+        const size_t pairs = (size_t)n * (size_t)s->dev.n_ents;
+        if (pairs == 0) return GI_OK;
+        if (pairs > (size_t)1 << 28) return fail(GI_ERR_ARG, "gi_kat_r_entities: more than 2^28 (ray, entity) pairs");
+        std::lock_guard<std::mutex> lk(s->mu);
+        int rc = bind_device(s->device);
+        if (rc) return rc;
+        const size_t rb = (size_t)n * 6 * sizeof(double), hb = pairs * sizeof(int32_t), pb = pairs * 6 * sizeof(double);
+        DevBuf d_r, d_h, d_p;
+        hipError_t e = d_r.alloc(rb);
+        if (e == hipSuccess) e = d_h.alloc(hb);
+        if (e == hipSuccess) e = d_p.alloc(pb);
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc (gi_kat_r_entities)");
+        e = hipMemcpy(d_r.p, rays, rb, hipMemcpyHostToDevice);
+        if (e == hipSuccess)
+            e = launch_r_entities_kat(s->dev, n, static_cast<const double*>(d_r.p), static_cast<int32_t*>(d_h.p),
+                                      static_cast<double*>(d_p.p), nullptr);
+        if (e == hipSuccess) e = hipMemcpy(hit, d_h.p, hb, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(pn, d_p.p, pb, hipMemcpyDeviceToHost);
+        return e == hipSuccess ? GI_OK : hip_fail(e, "gi_kat_r_entities");
+    });
+}
+
 int gi_kat_x_query(gi_scene* s, int n, const double* recs, const double cam_pos[3], int flags, int32_t* prim1, double* t1,
                    int32_t* occl, int32_t* skip_s, int32_t* prim2, double* t2, int32_t* skip2, double* skip_cos) {
     return guard([&]() -> int {

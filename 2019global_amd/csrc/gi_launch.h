@@ -85,7 +85,7 @@ hipError_t launch_adapt_init(const DevScene& sc, const CamDev& cam, int w, int h
 // (k_x_adapt_fold).
 hipError_t launch_adapt_fold(int w, int h, int s0, int e, const XAdaptPass& ap, const XScratch& xs, hipStream_t stream);
 
-// ---- gi_mode_r.hip: the Mode R kernels, k_trace_ray, k_box_kat ----
+// ---- gi_mode_r.hip: the Mode R kernels, k_trace_ray, k_box_kat, the primitive KATs ----
 RKernel r_kernel_choice(const DevScene& sc, const gi_opts& o);
 // the GI_RF_* values gi_mode_r.hip was compiled with: the build hands its -D flags to the kernel units only
 unsigned rf_own_pairs();
@@ -98,6 +98,12 @@ hipError_t launch_mode_r(const DevScene& sc, const CamDev& cam, V3 light, int w,
                          hipEvent_t ev_end);
 hipError_t launch_trace_ray(const DevScene& sc, V3 o, V3 d, V3 light, int32_t* out_i, double* out_d, hipStream_t stream);
 hipError_t launch_box_kat(int n, const double* recs, int32_t* out, hipStream_t stream);
+// gi_kat_r_prims: kind 0 tri_hit(TriRec) (tris: n host-built records), 1 sphere_hit, 2 box_hit, 3 r_box_test<4> with
+// 4 lanes per record; pn (6 doubles per record) is written for kinds 0 and 1 only
+hipError_t launch_r_prims_kat(int kind, int n, const double* recs, const TriRec* tris, int32_t* hit, double* pn,
+                              hipStream_t stream);
+// gi_kat_r_entities: n rays x sc.n_ents entities through ent_hit (the TRI instantiation for r_tri_only scenes)
+hipError_t launch_r_entities_kat(const DevScene& sc, int n, const double* rays, int32_t* hit, double* pn, hipStream_t stream);
 
 // ---- gi_wf.hip: k_wf_bounce, k_seg, k_cast, k_aov, k_rad, k_cam_rays, the query and texel KATs ----
 size_t wf_lds_bytes(const DevScene& sc, bool lds, bool flat);   // of k_wf_bounce and its kin, without the ring

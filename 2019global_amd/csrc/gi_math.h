@@ -56,7 +56,7 @@ GI_HD double sq3(V3 v) { return v.x * v.x + v.y * v.y + v.z * v.z; }
 GI_HD double smin(double a, double b) { return (b < a) ? b : a; }   // std::min
 GI_HD double smax(double a, double b) { return (a < b) ? b : a; }   // std::max
 GI_HD float sminf(float a, float b) { return (b < a) ? b : a; }
-GI_HD float fabsf_(float a) { return a < 0.0f ? -a : (a == 0.0f ? 0.0f : a); }
+GI_HD float fabsf_(float a) { return __builtin_fabsf(a); }   // std::abs: the sign bit cleared, of a NaN too
 
 // x86-64 cvttsd2si semantics for the reference's int() casts: NaN/out of range -> INT_MIN (A.9).
 // (gfx950's v_cvt_i32_f64 clamps instead, so this is explicit.)
@@ -108,10 +108,14 @@ GI_HD bool tri_accept(V3 p1, V3 p2, V3 p3, V3 pos, const float* e1f, const float
     // |d2 - d3|^2 < 1e-3, i.e. d1.d2 and d2.d3 > 0.9995, or a sub-normal shorter than 1e-3.  With every
     // |c_k| > 1e-100 the normalised d_k have length ~1 (no short one), and c1.c2 <= 0 or c2.c3 <= 0
     // (rounding errors ~1e-16 |c_i||c_j|) puts the pair ~90 degrees or more apart: the test below would
-    // reject too.  NaN / inf components fail the length guard or the comparison and take the full test.
+    // reject too.  A NaN fails the length guard or the comparison; a squared length of +inf (normalize
+    // then gives exact zeros, and the reference's length < 1e-3 branch accepts) fails the upper bound:
+    // both take the full test.
     const double n1 = dot(c1, c1), n2 = dot(c2, c2), n3 = dot(c3, c3);
     const double x12 = dot(c1, c2), x23 = dot(c2, c3);
-    if ((n1 > 1e-200) & (n2 > 1e-200) & (n3 > 1e-200) & ((x12 <= 0.0) | (x23 <= 0.0))) return false;
+    if ((n1 > 1e-200) & (n2 > 1e-200) & (n3 > 1e-200) & (n1 < 1e150) & (n2 < 1e150) & (n3 < 1e150) &
+        ((x12 <= 0.0) | (x23 <= 0.0)))
+        return false;
     // Both comparisons decided without the normalisations where the answer is clear.  With the
     // c_k's squared lengths in [1e-150, 1e150] the d_k are unit vectors to ~5u, so the computed
     // |d_j - d_k|^2 is 2 - 2 cos(c_j, c_k) to ~50u; cos^2 from the unnormalised dot products (relative

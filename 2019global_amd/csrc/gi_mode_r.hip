@@ -1235,6 +1235,61 @@ __global__ __launch_bounds__(256) void k_box_kat(int n, const double* recs, int3
                      normalize(v3(q[9], q[10], q[11]))) ? 1 : 0;
 }
 
+// Primitive-level known-answer kernels (gi_kat_r_prims): one record per lane through the functions the
+// Mode R kernels call, the direction normalised as k_box_kat does.  kind 0: tri_hit(const TriRec&) on the
+// host-built record (15 doubles p1 p2 p3 o dir); 1: sphere_hit (10 doubles pos radius o dir, the radius
+// narrowed to float as REnt stores it); 2: box_hit (12 doubles, k_box_kat's record).  pn (P, N; zeros on
+// a miss) is written for kinds 0 and 1.
+__global__ __launch_bounds__(256) void k_r_prims_kat(int kind, int n, const double* recs, const TriRec* tris,
+                                                     int32_t* hit, double* pn) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    V3 P = v3(0, 0, 0), N = v3(0, 0, 0);
+    bool h;
+    if (kind == 0) {
+        const double* q = recs + 15 * (size_t)i;
+        h = tri_hit(tris[i], v3(q[9], q[10], q[11]), normalize(v3(q[12], q[13], q[14])), P, N);
+    } else if (kind == 1) {
+        const double* q = recs + 10 * (size_t)i;
+        h = sphere_hit(v3(q[0], q[1], q[2]), (float)q[3], v3(q[4], q[5], q[6]), normalize(v3(q[7], q[8], q[9])), P, N);
+    } else {
+        const double* q = recs + 12 * (size_t)i;
+        h = box_hit(v3(q[0], q[1], q[2]), v3(q[3], q[4], q[5]), v3(q[6], q[7], q[8]), normalize(v3(q[9], q[10], q[11])));
+    }
+    hit[i] = h ? 1 : 0;
+    if (kind <= 1) {
+        double* w = pn + 6 * (size_t)i;
+        w[0] = P.x; w[1] = P.y; w[2] = P.z; w[3] = N.x; w[4] = N.y; w[5] = N.z;
+    }
+}
+// kind 3: k_rf_reach's grouped node test itself -- record i is held by the 4 consecutive lanes 4i .. 4i + 3
+// (a group lies inside one wave, and its lanes leave or stay together).
+__global__ __launch_bounds__(256) void k_r_box4_kat(int n, const double* recs, int32_t* hit) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long i = t >> 2;
+    if (i >= n) return;
+    const double* q = recs + 12 * (size_t)i;
+    const bool h = r_box_test<4>(v3(q[0], q[1], q[2]), v3(q[3], q[4], q[5]), v3(q[6], q[7], q[8]),
+                                 normalize(v3(q[9], q[10], q[11])));
+    if ((t & 3) == 0) hit[i] = h ? 1 : 0;
+}
+// gi_kat_r_entities: every ray (o, dir normalised here) against every entity through ent_hit, one pair
+// per lane; P and N start as zeros and are stored as ent_hit leaves them.
+template <bool TRI>
+__global__ __launch_bounds__(256) void k_r_entities_kat(DevScene sc, int n, const double* rays, int32_t* hit, double* pn) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= (long long)n * sc.n_ents) return;
+    const long long i = j / sc.n_ents;
+    const int k = (int)(j - i * sc.n_ents);
+    const double* q = rays + 6 * (size_t)i;
+    V3 P = v3(0, 0, 0), N = v3(0, 0, 0);
+    uint32_t nprim = 0;
+    const bool h = ent_hit<TRI>(sc, sc.ents[k], v3(q[0], q[1], q[2]), normalize(v3(q[3], q[4], q[5])), P, N, nprim);
+    hit[j] = h ? 1 : 0;
+    double* w = pn + 6 * (size_t)j;
+    w[0] = P.x; w[1] = P.y; w[2] = P.z; w[3] = N.x; w[4] = N.y; w[5] = N.z;
+}
+
 __global__ __launch_bounds__(64) void k_trace_ray(DevScene sc, V3 o, V3 d, V3 light, int32_t* out_i, double* out_d) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     RResult r;
@@ -1326,6 +1381,27 @@ hipError_t launch_mode_r(const DevScene& sc, const CamDev& cam, V3 light, int w,
 
 hipError_t launch_box_kat(int n, const double* recs, int32_t* out, hipStream_t stream) {
     if (n > 0) hipLaunchKernelGGL(k_box_kat, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, recs, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_r_prims_kat(int kind, int n, const double* recs, const TriRec* tris, int32_t* hit, double* pn,
+                              hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    if (kind == 3)
+        hipLaunchKernelGGL(k_r_box4_kat, dim3((unsigned)((4ll * n + 255) / 256)), dim3(256), 0, stream, n, recs, hit);
+    else
+        hipLaunchKernelGGL(k_r_prims_kat, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, kind, n, recs, tris, hit, pn);
+    return hipGetLastError();
+}
+
+hipError_t launch_r_entities_kat(const DevScene& sc, int n, const double* rays, int32_t* hit, double* pn, hipStream_t stream) {
+    const long long pairs = (long long)n * sc.n_ents;
+    if (pairs <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((pairs + 255) / 256));
+    if (sc.r_tri_only)
+        hipLaunchKernelGGL(k_r_entities_kat<true>, grid, dim3(256), 0, stream, sc, n, rays, hit, pn);
+    else
+        hipLaunchKernelGGL(k_r_entities_kat<false>, grid, dim3(256), 0, stream, sc, n, rays, hit, pn);
     return hipGetLastError();
 }
 

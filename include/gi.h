@@ -869,6 +869,29 @@ int gi_obj_parse(const char* text, int64_t len, const gi_entity_desc* tmpl, gi_e
  * it) over n host records (min[3], max[3], origin[3], dir[3]); out[i] = 0/1. */
 int gi_kat_expbox(int n, const double* recs, int32_t* out);
 
+/* Known-answer hooks (TEST hooks): Mode R's primitive tests record by record, through the functions
+ * the Mode R kernels call.  n host records; dir is normalised as the reference's Ray constructor does
+ * (ray.h:6); hit[i] = 0/1; pn[6 i ..] = the point and normal, zeros on a miss.  kind:
+ *   GI_KAT_R_TRI    15 doubles p1 p2 p3 o dir: the builder's triangle record (its normal, centre and fp32
+ *                   edges, made on the host) through the prefiltered ImpTriangle test ent_hit calls;
+ *   GI_KAT_R_SPHERE 10 doubles pos radius o dir: ImpSphere::intersect, the radius narrowed to float;
+ *   GI_KAT_R_BOX    12 doubles min max o dir: the ExpBox node test of one lane (gi_kat_expbox's);
+ *   GI_KAT_R_BOX4   the same records, each held by 4 consecutive lanes and decided by the grouped
+ *                   node test of the flat Mode R phases (3 of the 12 faces per lane, a ballot).
+ * pn is written for triangles and spheres only (may be NULL for boxes).  n = 0 launches nothing. */
+#define GI_KAT_R_TRI 0
+#define GI_KAT_R_SPHERE 1
+#define GI_KAT_R_BOX 2
+#define GI_KAT_R_BOX4 3
+int gi_kat_r_prims(int kind, int n, const double* recs, int32_t* hit, double* pn);
+
+/* Known-answer hook (a TEST hook): n host rays (o[3], dir[3]; dir normalised here) each against every
+ * entity of the scene through the Mode R kernels' entity test, in the instantiation they use for this
+ * scene.  hit[i * E + k] = 0/1 and pn[6 (i * E + k) ..] = the point and normal of ray i on entity k
+ * (E entities in push order): both start as zeros and are stored as Entity::intersect leaves them (the
+ * triangle groups overwrite them on a miss, entities.h:616-617).  No texture coordinates. */
+int gi_kat_r_entities(gi_scene* s, int n, const double* rays, int32_t* hit, double* pn);
+
 /* Known-answer hook (a TEST hook; ABI 11): the Mode X device queries ray by ray.  n host records of
  * 12 doubles -- o[3], d[3], light[3], d2[3]; d and d2 are used as given -- each run as one path
  * segment's three queries by the kernel variant the segment form (k_seg) runs for this scene, the

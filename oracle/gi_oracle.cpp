@@ -1442,6 +1442,36 @@ int gio_boxes(int n, const double* recs, int32_t* out) {
     return 0;
 }
 
+// Primitive-level known answers (tests/r_prims_cases.py): the oracle's own ImpTriangle, ImpSphere and
+// ExpBox routines over n records -- kind 0: 15 doubles p1 p2 p3 o dir; 1: 10 doubles pos radius o dir;
+// 2: 12 doubles min max o dir.  dir is normalised as Ray's constructor does (ray.h:6); P and N start as
+// zeros.  hit[i] = 0/1, pn[6 i ..] = P, N (not written for boxes; may be null there).
+int gio_prims(int kind, int n, const double* recs, int32_t* hit, double* pn) {
+    if (kind < 0 || kind > 2 || n < 0 || (n > 0 && (!recs || !hit || (kind < 2 && !pn)))) { g_err = "bad arguments"; return -2; }
+#pragma omp parallel for schedule(static)
+    for (int i = 0; i < n; ++i) {
+        V3 P{0, 0, 0}, N{0, 0, 0};
+        bool h;
+        if (kind == 0) {
+            const double* q = recs + 15 * (size_t)i;
+            h = tri_intersect(make_tri({q[0], q[1], q[2]}, {q[3], q[4], q[5]}, {q[6], q[7], q[8]}), {q[9], q[10], q[11]},
+                              normalize(V3{q[12], q[13], q[14]}), P, N);
+        } else if (kind == 1) {
+            const double* q = recs + 10 * (size_t)i;
+            h = sphere_intersect({q[0], q[1], q[2]}, (float)q[3], {q[4], q[5], q[6]}, normalize(V3{q[7], q[8], q[9]}), P, N);
+        } else {
+            const double* q = recs + 12 * (size_t)i;
+            h = box_hit({q[0], q[1], q[2]}, {q[3], q[4], q[5]}, {q[6], q[7], q[8]}, normalize(V3{q[9], q[10], q[11]}));
+        }
+        hit[i] = h ? 1 : 0;
+        if (kind < 2) {
+            double* w = pn + 6 * (size_t)i;
+            w[0] = P.x; w[1] = P.y; w[2] = P.z; w[3] = N.x; w[4] = N.y; w[5] = N.z;
+        }
+    }
+    return 0;
+}
+
 // Ray-level Mode X queries (the known-answer reference of the device hook gi_kat_x_query): per
 // record the three queries of one path segment of sample_mode_x, with the same operations --
 // closest hit of (o, d); from its point P the shadow query toward `light`; the closest hit of

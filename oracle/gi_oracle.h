@@ -45,6 +45,10 @@ int gio_rays(const char* scn, int n, const double* rays, int32_t* out_hit, doubl
 
 // ExpBox node test over n x (min[3], max[3], origin[3], dir[3]) records.
 int gio_boxes(int n, const double* recs, int32_t* out);
+// Primitive-level known answers: kind 0 triangles (15 doubles p1 p2 p3 o dir), 1 spheres (10 doubles pos
+// radius o dir), 2 boxes (12 doubles min max o dir); dir normalised, P and N start as zeros.  hit[i] = 0/1,
+// pn[6 i ..] = P, N (triangles and spheres only).
+int gio_prims(int kind, int n, const double* recs, int32_t* hit, double* pn);
 
 // Mode X closest-hit / shadow queries: -1 (default) = this oracle's BVH above 256 primitives,
 // brute force below; 0 = brute force always; 1 = BVH always.  Same results either way (tested).

@@ -14,6 +14,8 @@
 //   tree    <scene.scn>                 octree structure dump (octree.h:75-129), DFS order
 //   rays    <scene.scn> <rays.bin> <out.bin>   per-entity intersect KAT over a ray list
 //   boxes   <boxes.bin> <out.bin>       ExpBox node test (entities.h:379-440) over (box, ray) pairs
+//   tris    <tris.bin> <out.bin>        ImpTriangle::intersect (entities.h:150-249) over (triangle, ray) pairs
+//   spheres <spheres.bin> <out.bin>     ImpSphere::intersect (entities.h:53-96) over (sphere, ray) pairs
 //   kat                                 main.cpp:90-133 ad-hoc test functions, printed at %.17g
 //   time    <scene.scn> <w> <h> [stride]   wall time of the per-pixel loop (CPU baseline)
 #include <cstdio>
@@ -300,6 +302,67 @@ static int cmd_boxes(char** argv) {
     return 0;
 }
 
+// Per record int32 hit, then P[3], N[3] as doubles (both start as zeros): the output of `tris` and `spheres`.
+static void put_hit_pn(FILE* o, bool hit, const glm::dvec3& p, const glm::dvec3& nn) {
+    const int32_t h = hit ? 1 : 0;
+    const double pn[6] = {p.x, p.y, p.z, nn.x, nn.y, nn.z};
+    fwrite(&h, 4, 1, o);
+    fwrite(pn, 8, 6, o);
+}
+
+// Reads int32 n, then n records of `width` doubles.
+static bool read_recs(const char* path, int width, int32_t& n, std::vector<double>& b) {
+    FILE* f = fopen(path, "rb");
+    if (!f) return false;
+    n = 0;
+    bool ok = fread(&n, 4, 1, f) == 1 && n >= 0;
+    if (ok) {
+        b.resize((size_t)n * width);
+        ok = fread(b.data(), 8, b.size(), f) == b.size();
+    }
+    fclose(f);
+    return ok;
+}
+
+// tris.bin: int32 n, then n x (p1[3], p2[3], p3[3], origin[3], dir[3]); dir goes through Ray's ctor.
+static int cmd_tris(char** argv) {
+    int32_t n = 0;
+    std::vector<double> b;
+    if (!read_recs(argv[2], 15, n, b)) return 1;
+    FILE* o = fopen(argv[3], "wb");
+    if (!o) return 1;
+    for (int i = 0; i < n; ++i) {
+        const double* q = &b[15 * (size_t)i];
+        ImpTriangle t({q[0], q[1], q[2]}, {q[3], q[4], q[5]}, {q[6], q[7], q[8]});
+        Ray r({q[9], q[10], q[11]}, {q[12], q[13], q[14]});
+        glm::dvec3 p{0, 0, 0}, nn{0, 0, 0};
+        const bool hit = t.intersect(r, p, nn);
+        put_hit_pn(o, hit, p, nn);
+    }
+    fclose(o);
+    return 0;
+}
+
+// spheres.bin: int32 n, then n x (pos[3], radius, origin[3], dir[3]); the radius narrows to the
+// constructor's float parameter.
+static int cmd_spheres(char** argv) {
+    int32_t n = 0;
+    std::vector<double> b;
+    if (!read_recs(argv[2], 10, n, b)) return 1;
+    FILE* o = fopen(argv[3], "wb");
+    if (!o) return 1;
+    for (int i = 0; i < n; ++i) {
+        const double* q = &b[10 * (size_t)i];
+        ImpSphere s({q[0], q[1], q[2]}, (float)q[3], {1, 0, 0});
+        Ray r({q[4], q[5], q[6]}, {q[7], q[8], q[9]});
+        glm::dvec3 p{0, 0, 0}, nn{0, 0, 0};
+        const bool hit = s.intersect(r, p, nn);
+        put_hit_pn(o, hit, p, nn);
+    }
+    fclose(o);
+    return 0;
+}
+
 static void pv(const char* name, glm::dvec3 v) { printf("%s %.17g %.17g %.17g\n", name, v.x, v.y, v.z); }
 
 static int cmd_kat() {
@@ -349,12 +412,14 @@ static int cmd_time(int argc, char** argv) {
 }
 
 int main(int argc, char** argv) {
-    if (argc < 2) { fprintf(stderr, "usage: ref_harness render|tree|rays|boxes|kat|time ...\n"); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: ref_harness render|tree|rays|boxes|tris|spheres|kat|time ...\n"); return 2; }
     std::string c = argv[1];
     if (c == "render" && argc >= 6) return cmd_render(argc, argv);
     if (c == "tree" && argc >= 3) return cmd_tree(argv);
     if (c == "rays" && argc >= 5) return cmd_rays(argv);
     if (c == "boxes" && argc >= 4) return cmd_boxes(argv);
+    if (c == "tris" && argc >= 4) return cmd_tris(argv);
+    if (c == "spheres" && argc >= 4) return cmd_spheres(argv);
     if (c == "kat") return cmd_kat();
     if (c == "time" && argc >= 5) return cmd_time(argc, argv);
     fprintf(stderr, "bad arguments\n");

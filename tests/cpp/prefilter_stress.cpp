@@ -81,6 +81,22 @@ int main(int argc, char** argv) {
         if (r != f || r != u || rs != us || rs != fs) { ++bad; if (bad < 5) printf("mismatch it=%ld mode=%d raw=%d full=%d\n", it, mode, r, u); }
         if (mode == 2) near += r;
     }
+    // magnitudes past fp32's range (the solve's casts and products overflow: inf and NaN reach the early exits'
+    // guards) and up to 1e77, where a squared length overflows fp64; the answer must stay full()'s
+    long nov = 0, ovhits = 0;
+    for (long it = 0; it < N / 8; ++it) {
+        const double ex[6] = {1e77, 1e18, 1e30, 1e38, 1e19, 3e18};
+        const double sc = ex[it % 6] * std::pow(10.0, U(g)), oc = (it % 12 < 6) ? sc * 20 : 1e38 * std::pow(10.0, U(g));
+        const V3 p1 = v3(U(g), U(g), U(g)) * sc, p2 = v3(U(g), U(g), U(g)) * sc, p3 = v3(U(g), U(g), U(g)) * sc;
+        const V3 o = v3(U(g), U(g), U(g)) * oc;
+        const double a = (U(g) + 1) / 2, b = (U(g) + 1) / 2 * (1 - a);
+        const V3 tgt = (it % 2) ? p1 + (p2 - p1) * a + (p3 - p1) * b : v3(U(g), U(g), U(g)) * (sc * 2);
+        const V3 d = normalize(tgt - o);
+        const bool r = raw(p1, p2, p3, o, d), f = tri_hit_corners(p1, p2, p3, o, d), u = full(p1, p2, p3, o, d);
+        ++nov; ovhits += u;
+        if (r != u || f != u) { ++bad; if (bad < 5) printf("overflow mismatch it=%ld raw=%d corners=%d full=%d\n", it, r, f, u); }
+    }
+    printf("overflow cases %ld hits %ld\n", nov, ovhits);
     // box_hit_part: the OR of its four parts (3 faces each, for four cooperating lanes) is box_hit
     long nb = 0, bhits = 0, bbad = 0;
     for (long it = 0; it < N / 8; ++it) {

@@ -11,6 +11,9 @@ Fixtures are data only (inputs and the reference's outputs):
   tree_<scene>.json     octree statistics + sha256 of the `tree` dump (octree.h structure)
   rays_<scene>.npz      per-(ray, entity) intersect/getTextureCoord KAT on seeded random rays
   boxes.npz             ExpBox node-test KAT (entities.h:379-440) on seeded random boxes/rays
+  adv_<kind>.npz        (`adversarial`) the primitive tests on tests/r_prims_cases.py's adversarial records, digests
+                        only: the records' sha256, the classes and their sizes, the reference's packed hit bits, hit
+                        count per class, sha256 of P|N per block of 512 cases and P, N of each class's first 64 hits
   rcam_<scene>.npz      (`cameras`) whole 40 x 28 Mode R frames from the camera placements of
                         tests/r_cameras.py, stacked per scene: per placement its pos, look-at, focal, w, h and
                         the reference's rgb / hit / uv / ncand / nnode / q
@@ -224,9 +227,59 @@ def make_cameras():
         print("cameras", scene, len(meta["placements"]), "frames,", size, "bytes" + (" (over the limit: not kept)" if size >= limit else ""))
 
 
+# Primitive-level parity (tests/test_r_prims_host.py, tests/test_gpu_r_prims.py): the compiled reference's
+# ImpTriangle / ExpBox / ImpSphere answers on r_prims_cases' records.  The records are regenerated by the tests (their
+# sha256 is stored), the answers are kept as digests (oracle_util.prims_summary).  The classes aimed at a decision
+# boundary must hold both answers in numbers, judged on the reference's answers alone.
+BOUNDARY = {"tris": ("band", "near_edge", "near_parallel", "fp32_parallel"), "boxes": ("near_face",), "spheres": ("tangent",)}
+
+
+def write_npz(path: str, arrays: dict):
+    """np.savez_compressed without the wall clock in the zip headers: the same arrays give the same bytes."""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for name in sorted(arrays):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(arrays[name]), allow_pickle=False)
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue())
+
+
+def make_adversarial():
+    import r_prims_cases as C
+    limit = os.path.getsize(os.path.join(HERE, "boxes.npz"))
+    for kind in C.KINDS:
+        recs, names, cls = C.cases(kind)
+        if kind == "boxes":
+            ref = dict(hit=U.ref_boxes(recs), pn=np.zeros((recs.shape[0], 6)))
+        else:
+            ref = (U.ref_tris if kind == "tris" else U.ref_spheres)(recs)
+        counts = np.array([int((cls == k).sum()) for k in range(len(names))], np.int64)
+        s = U.prims_summary(ref["hit"], ref["pn"], cls, len(names))
+        for name in BOUNDARY[kind]:
+            k = names.index(name)
+            hits, misses = int(s["class_hits"][k]), int(counts[k] - s["class_hits"][k])
+            assert hits >= 1000 and misses >= 1000, (kind, name, hits, misses)
+            if name == "band":
+                assert 0.2 <= hits / counts[k] <= 0.8, (name, hits, int(counts[k]))
+        path = os.path.join(HERE, f"adv_{kind}.npz")
+        write_npz(path, dict(inputs_sha256=np.array(C.digest(recs)), class_names=np.array(names), class_counts=counts, **s))
+        size = os.path.getsize(path)
+        assert size < limit, (path, size, limit)
+        print("adversarial", kind, recs.shape[0], "cases,", int(ref["hit"].sum()), "hits,", size, "bytes")
+        for k, name in enumerate(names):
+            print("   %-16s %6d cases %6d hits" % (name, counts[k], s["class_hits"][k]))
+
+
 if __name__ == "__main__":
     if not U.have_ref():
         sys.exit("oracle/_ref/ref_harness missing: run `make -C oracle ref` where /root/reference exists")
+    if sys.argv[1:] == ["adversarial"]:   # the primitive tests' adversarial classes only
+        make_adversarial()
+        sys.exit(0)
     if sys.argv[1:] == ["cameras"]:   # the camera placements' frames only
         make_cameras()
         sys.exit(0)

@@ -49,6 +49,7 @@ def oracle():
         lib.gio_tree.restype = ctypes.c_long
         lib.gio_rays.argtypes = [ctypes.c_char_p, ctypes.c_int, f64p, i32p, f64p, i32p]
         lib.gio_boxes.argtypes = [ctypes.c_int, f64p, i32p]
+        lib.gio_prims.argtypes = [ctypes.c_int, ctypes.c_int, f64p, i32p, f64p]
         lib.gio_last_error.restype = ctypes.c_char_p
         lib.gio_set_accel.argtypes = [ctypes.c_int]
         lib.gio_set_no_shadow.argtypes = [ctypes.c_int]
@@ -155,6 +156,89 @@ def oracle_boxes(recs: np.ndarray) -> np.ndarray:
     return out
 
 
+PRIM_KINDS = {"tris": (0, 15), "spheres": (1, 10), "boxes": (2, 12)}   # kind -> (gio_prims kind, record width)
+
+
+def oracle_prims(kind: str, recs: np.ndarray) -> dict:
+    """The oracle's own primitive routines over r_prims_cases records (gio_prims): hit (n,) int32 and
+    pn (n, 6) = P, N, zeros on a miss and for boxes."""
+    k, width = PRIM_KINDS[kind]
+    recs = np.ascontiguousarray(recs, np.float64).reshape(-1, width)
+    n = recs.shape[0]
+    hit = np.zeros(n, np.int32)
+    pn = np.zeros((n, 6))
+    rc = oracle().gio_prims(k, n, _p(recs, ctypes.c_double), _p(hit, ctypes.c_int32), _p(pn, ctypes.c_double) if k < 2 else None)
+    assert rc == 0, rc
+    return dict(hit=hit, pn=pn)
+
+
+PRIM_BLOCK, PRIM_SAMPLES = 512, 64
+
+
+def prims_summary(hit: np.ndarray, pn: np.ndarray, cls: np.ndarray, n_classes: int) -> dict:
+    """What tests/golden/adv_*.npz keep of a primitive run (make_golden.py `adversarial`): the packed hit
+    bits, the hit count per class, the sha256 of the P|N bit patterns of every block of PRIM_BLOCK cases
+    (misses contribute their zeros) and P, N in full for the first PRIM_SAMPLES hits of every class."""
+    hit = np.ascontiguousarray(hit, np.int32)
+    pn = np.ascontiguousarray(pn, "<f8").reshape(-1, 6)
+    n = hit.shape[0]
+    blocks = np.array([np.frombuffer(hashlib.sha256(pn[b:b + PRIM_BLOCK].tobytes()).digest(), np.uint8)
+                       for b in range(0, n, PRIM_BLOCK)])
+    idx = np.concatenate([np.flatnonzero((cls == k) & (hit != 0))[:PRIM_SAMPLES] for k in range(n_classes)])
+    return dict(hit_bits=np.packbits(hit != 0), class_hits=np.array([int(hit[cls == k].sum()) for k in range(n_classes)], np.int64),
+                block_sha256=blocks, sample_index=idx.astype(np.int64), sample_pn=pn[idx].view("<u8"))
+
+
+_prims_expected: dict = {}
+
+
+def prims_expected(kind: str) -> dict:
+    """The adversarial records of `kind` with the oracle's per-case answers, after the two checks that make
+    them the compiled reference's: the generator's sha256 equals the fixture's, and the oracle's summary equals
+    the fixture's (hit bits, per-class hit counts, every block digest, the stored P, N samples).  Computed once
+    per process; the arrays are read-only."""
+    if kind not in _prims_expected:
+        import r_prims_cases as C
+        z = np.load(os.path.join(GOLDEN, f"adv_{kind}.npz"))
+        recs, names, cls = C.cases(kind)
+        assert C.digest(recs) == str(z["inputs_sha256"]), f"{kind}: r_prims_cases no longer generates the fixture's records"
+        assert names == [str(x) for x in z["class_names"]]
+        assert [int((cls == k).sum()) for k in range(len(names))] == z["class_counts"].tolist()
+        o = oracle_prims(kind, recs)
+        s = prims_summary(o["hit"], o["pn"], cls, len(names))
+        ref_hit = np.unpackbits(z["hit_bits"])[:recs.shape[0]]
+        bad = np.flatnonzero(ref_hit != (o["hit"] != 0))
+        assert bad.size == 0, (f"{kind}: the oracle's hit differs from the reference's on {bad.size} cases; first: case {bad[0]} "
+                               f"class {names[cls[bad[0]]]} record {recs[bad[0]].tolist()} reference {ref_hit[bad[0]]} oracle {o['hit'][bad[0]]}")
+        assert s["class_hits"].tolist() == z["class_hits"].tolist()
+        blk = np.flatnonzero((s["block_sha256"] != z["block_sha256"]).any(1))
+        assert blk.size == 0, f"{kind}: the oracle's P|N differ from the reference's in {blk.size} blocks of {PRIM_BLOCK}; first block {blk[:1]}"
+        assert (s["sample_index"] == z["sample_index"]).all() and (s["sample_pn"] == z["sample_pn"]).all()
+        for a in (o["hit"], o["pn"]):
+            a.setflags(write=False)
+        _prims_expected[kind] = dict(recs=recs, names=names, cls=cls, hit=o["hit"], pn=o["pn"])
+    return _prims_expected[kind]
+
+
+def assert_prims_equal(kind: str, what: str, hit: np.ndarray, pn=None, n=None) -> None:
+    """`hit` (and `pn`, bit for bit) of the first n adversarial cases equal the oracle's on every case: nothing
+    excluded, no tolerance.  A failure names the first differing case."""
+    e = prims_expected(kind)
+    n = e["recs"].shape[0] if n is None else n
+    hit = np.asarray(hit).reshape(-1)
+    assert hit.shape[0] == n
+    bad = (hit != 0) != (e["hit"][:n] != 0)
+    if pn is not None:
+        bad |= ~bits_equal(np.asarray(pn).reshape(n, 6), e["pn"][:n]).all(1)
+    idx = np.flatnonzero(bad)
+    if idx.size:
+        i = int(idx[0])
+        per = {e["names"][k]: int((e["cls"][idx] == k).sum()) for k in sorted(set(e["cls"][idx].tolist()))}
+        raise AssertionError(f"{kind} / {what}: {idx.size} of {n} cases differ from the oracle, by class {per}; first: case {i} class "
+                             f"{e['names'][e['cls'][i]]} record {e['recs'][i].tolist()} got hit {int(hit[i])} pn "
+                             f"{None if pn is None else np.asarray(pn).reshape(n, 6)[i].tolist()} expected hit {int(e['hit'][i])} pn {e['pn'][i].tolist()}")
+
+
 # ---- compiled reference (oracle/_ref) -------------------------------------------------------
 
 def have_ref() -> bool:
@@ -224,6 +308,28 @@ def ref_boxes(recs: np.ndarray) -> np.ndarray:
             f.write(np.ascontiguousarray(recs, "<f8").tobytes())
         subprocess.run([REF_HARNESS, "boxes", rp, op], check=True)
         return np.frombuffer(open(op, "rb").read(), dtype="<i4").copy()
+
+
+def _ref_prims(mode: str, recs: np.ndarray) -> dict:
+    with tempfile.TemporaryDirectory() as td:
+        rp, op = os.path.join(td, "r.bin"), os.path.join(td, "o.bin")
+        with open(rp, "wb") as f:
+            f.write(struct.pack("<i", recs.shape[0]))
+            f.write(np.ascontiguousarray(recs, "<f8").tobytes())
+        subprocess.run([REF_HARNESS, mode, rp, op], check=True)
+        a = np.fromfile(op, dtype=np.dtype([("hit", "<i4"), ("pn", "<f8", 6)]))
+        assert a.shape[0] == recs.shape[0]
+        return dict(hit=a["hit"].copy(), pn=a["pn"].copy())
+
+
+def ref_tris(recs: np.ndarray) -> dict:
+    """ImpTriangle::intersect over records p1 p2 p3 o dir (15 doubles): hit, pn = P, N (zeros on a miss)."""
+    return _ref_prims("tris", np.asarray(recs).reshape(-1, 15))
+
+
+def ref_spheres(recs: np.ndarray) -> dict:
+    """ImpSphere::intersect over records pos radius o dir (10 doubles): hit, pn = P, N (zeros on a miss)."""
+    return _ref_prims("spheres", np.asarray(recs).reshape(-1, 10))
 
 
 def dropin_demo() -> str:
